@@ -12,7 +12,11 @@ in HBM before the timed region and every output buffer is allocated before it; w
 Rank 0 prints ONE JSON line.  `value` = images of all ranks / wall time of the K timed steps (barrier + synchronize on both
 sides, max over ranks); `ms_per_step_median` is the median of the per-step HIP-event times on the launch stream.
 
-Besides the headline (bf16 speed mode) the same line carries
+A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = wall milliseconds of one timed step).
+`--dump-outputs DIR` writes what the last timed step computed (decoded boxes and feature rows per tile in map order, their counts,
+the heatmap with its NMS peak mask and a fixed seeded sample of the feature map; with --train the loss and a sample of the gradients) as DIR/<name>.npy, all finite.
+With `--full` (what the --no-* options prune) the same line also carries the one-stream and sustained rates, the other numeric
+modes, seams 2 and 3, config3_b32, train_step and
   parity      -- L-inf / peak-set agreement of image 0 of the timed batch against the CPU oracle, for the timed bf16 model AND for
                  the fp32 parity mode and the fp16 mode (whose own images/s are reported there: they are different programs);
   roofline    -- the kernel with the largest share of the forward, HIP-event timed inside this run;
@@ -224,6 +228,57 @@ def train_dry_run(args, rank, world):
         dist.destroy_process_group()
 
 
+DUMP_ARRAY_BYTES = 12 << 20                  # --dump-outputs: an array above this is replaced by a fixed, seeded sample of this size
+DUMP_TOTAL_BYTES = 64_000_000                # ... and all files of one run together (the detector's come to ~33 MB on one GPU)
+
+
+def dump_outputs(out_dir: str, arrays) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array (float32 stays float32, anything else becomes float64).  An array above
+    DUMP_ARRAY_BYTES is written as the elements at a fixed, seeded set of flat positions (sorted), the same in every run of the same
+    shape, so that two builds can be compared element for element.  Every value written is finite (a non-finite output is an error,
+    not something to compare), and the files stay within DUMP_TOTAL_BYTES in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        if not np.isfinite(a).all():
+            raise ValueError(f"--dump-outputs: {name} has {int((~np.isfinite(a)).sum())} non-finite values")
+        if a.nbytes > DUMP_ARRAY_BYTES:
+            k = DUMP_ARRAY_BYTES // a.itemsize
+            idx = np.sort(np.random.default_rng(20240607).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        if total > DUMP_TOTAL_BYTES:
+            raise ValueError(f"--dump-outputs: more than {DUMP_TOTAL_BYTES} bytes at {name}")
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
+def decoded_arrays(counts: torch.Tensor, records: torch.Tensor, feat0: int = 12):
+    """The boxes and feature rows a caller of the decode receives, made comparable across runs: rows past a tile's count (whatever an
+    earlier step left in the reused block) are zeroed, and each tile's rows are put in map order (iy, then ix)."""
+    cnt = counts.cpu().numpy().astype(np.int64)
+    rec = records.float().cpu().numpy()
+    boxes = np.zeros(rec.shape[:2] + (9,), np.float32)
+    feats = np.zeros(rec.shape[:2] + (rec.shape[2] - feat0,), np.float32)
+    for b in range(rec.shape[0]):
+        n = int(min(cnt[b], rec.shape[1]))
+        r = rec[b, :n]
+        order = np.lexsort((r[:, 1], r[:, 2]))
+        boxes[b, :n] = r[order, :9]
+        feats[b, :n] = r[order, feat0:]
+    return {"counts": cnt, "boxes": boxes, "box_features": feats}
+
+
+def heatmap_arrays(heat_nhwc: torch.Tensor):
+    """The NMS'd heatmap [B,h,w,10] in finite form: channel 1 holds the logit at a 3x3 peak and -inf elsewhere (the reference's
+    `minval`); that channel's -inf entries are written as 0 and the peak positions as their own 0/1 map."""
+    hm = heat_nhwc.cpu().numpy().copy()
+    peak = np.isfinite(hm[..., 1])
+    hm[..., 1][~peak] = 0.0
+    return {"heatmap": hm, "nms_peak_mask": peak.astype(np.float32)}
+
+
 def emit_last_line(result) -> None:
     """The ONE JSON line, as the last thing on stdout: RCCL writes its version banner through C stdio, which (piped) is flushed at exit,
     i.e. AFTER anything Python printed earlier -- flush the C buffers first, print after the process group is gone."""
@@ -293,6 +348,8 @@ def train_bench(args, rank, local_rank, world, emit=True):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     loss = float(state["loss"])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": np.array([loss]), "gradients": ts.grads.float().cpu().numpy()})
     if rank != 0:
         if dist_on:
             dist.barrier()
@@ -314,7 +371,7 @@ def train_bench(args, rank, local_rank, world, emit=True):
               "train_gflop_per_image_dense": round(3 * GFLOP_PER_IMAGE, 1),
               "path_tflops_per_gpu": round(value / world * 3 * GFLOP_PER_IMAGE / 1000, 2),
               "path_frac_of_mfma_peak": round(value / world * 3 * GFLOP_PER_IMAGE / 1000 / PEAK[args.precision], 4)}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         lib = L.load()
         n_ops = plan["n_ops"]
         ms = (C.c_float * n_ops)()
@@ -359,7 +416,7 @@ def train_bench(args, rank, local_rank, world, emit=True):
         del ts, opt, model
         torch.cuda.empty_cache()
         return result
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # the CPU oracle of the same step (torch autograd, fp32) on a bounded sample: batch 1, 384x384 (a quarter of a tile), once
         from oracle import train_oracle
         torch.set_num_threads(min(16, os.cpu_count() or 1))
@@ -389,13 +446,17 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=60.0, help="seconds of CPU-oracle time to aim for")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event pass")
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 parity-mode record")
-    ap.add_argument("--dump-ops", default="", help="write per-op timings (JSON) to this path")
+    ap.add_argument("--dump-ops", default="", help="with --full: write per-op timings (JSON) to this path")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo walk through the N-rank control flow (no GPU work)")
     ap.add_argument("--lanes", type=int, default=2, help="successive batches alternate over this many HIP streams (1 = one stream)")
     ap.add_argument("--no-seam2", action="store_true", help="skip the batch-1 host-in / host-out call_detector latency record")
     ap.add_argument("--no-sustained", action="store_true", help="skip the >= 300-step / >= 4 s sustained-rate record")
     ap.add_argument("--train", action="store_true", help="BASELINE configs[4]: the train step (fwd + loss + bwd + optimizer, DDP all-reduce when N > 1)")
     ap.add_argument("--no-configs", action="store_true", help="skip the config3_b32 (batch 32 + decode + gather) and train_step (5 steps) records of the default line")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: one-stream and sustained rates, per-kernel roofline, the other "
+                                                          "precisions, seams 2 and 3, CPU baseline and parity, config3_b32, train_step (the --no-* options "
+                                                          "prune it); without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32/float64)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -511,9 +572,16 @@ def main():
     # per-step HIP events: with lanes, event i+1 is recorded on the lane that ran step i, so consecutive events of ONE lane are `lanes` steps apart
     nl = lanes.n if lanes is not None else 1
     step_ms = [ev[i].elapsed_time(ev[i + nl]) / nl for i in range(1 if nl > 1 else 0, args.steps + 1 - nl)] or [1000 * el / args.steps]
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's outputs: its decoded boxes + feature rows (all ranks' tiles when gathered) and this rank's maps
+        li = (lanes.k - 1) % lanes.n if lanes is not None else None
+        arrays = decoded_arrays(out.counts, out.records)
+        arrays.update(heatmap_arrays(lanes.heat[li] if lanes is not None else heat))
+        arrays["feature_map"] = (lanes.feat[li] if lanes is not None else feat).cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     # the same K steps on ONE stream (no overlap between batches): reported beside the headline
     single = None
-    if lanes is not None:
+    if lanes is not None and args.full:
         for _ in range(2):
             single_step()
         if dist_on:
@@ -538,7 +606,7 @@ def main():
     peaks = float(out.counts.float().mean().item())
 
     # ---- sustained rate: >= 300 steps and >= 4 s (the 20-step burst above lasts 0.3 s; the part's clock settles over seconds) ----
-    sus_steps = max(300, int(4.0 / max(1e-4, el / args.steps)) + 1) if not args.no_sustained else 0
+    sus_steps = max(300, int(4.0 / max(1e-4, el / args.steps)) + 1) if args.full and not args.no_sustained else 0
     sus = None
     if sus_steps:
         if dist_on:
@@ -675,14 +743,14 @@ def main():
                 json.dump({"by_kernel": by, "ops": ops}, f, indent=1)
         return roof, allconv, round(total_ms, 3)
 
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         roof, allconv, total_ms = kernel_profile(model, x, heat, feat, args.precision, max(3, min(args.steps, 10)), args.dump_ops)
         result["roofline"] = roof
         result["all_conv_kernels"] = allconv
         result["forward_ms_sum_of_kernels"] = total_ms
 
     # ---- the other numeric mode, parity of both against the CPU oracle, CPU baseline (rank 0, N = 1) -------------
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         others = [] if args.no_fp32 else [p_ for p_ in ("fp32", "fp16x3", "fp16", "bf16") if p_ != args.precision]
         recs, maps = {}, {}
         for other in others:
@@ -919,7 +987,8 @@ def main():
             try:
                 lanes = None                                     # (the lanes' arenas go back to the allocator before the train step's 30 GB arena is made)
                 torch.cuda.empty_cache()
-                ta = argparse.Namespace(batch=B, steps=5, warmup=2, precision=args.precision, no_profile=args.no_profile, no_cpu_baseline=True)
+                ta = argparse.Namespace(batch=B, steps=5, warmup=2, precision=args.precision, no_profile=args.no_profile, no_cpu_baseline=True,
+                                        full=True, dump_outputs="")
                 tr = train_bench(ta, 0, local_rank, 1, emit=False)
                 result["train_step"] = {k: tr[k] for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "ms_per_step_median", "dtype", "finite",
                                                            "loss_last_step", "path_tflops_per_gpu", "path_frac_of_mfma_peak", "roofline", "kernel_time_by_label_ms",

@@ -7,6 +7,8 @@ import socket
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -87,3 +89,39 @@ def test_mismatched_world_size_is_refused():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"], capture_output=True, text=True, timeout=120,
                        cwd=ROOT, env=env)
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
+
+
+def test_dump_outputs_writes_comparable_float_arrays(tmp_path):
+    """The --dump-outputs helpers on CPU tensors: rows past a tile's count are zeroed and the rest put in map order, integers become
+    float64, and an array above the size cap becomes the same seeded sample in every run."""
+    import numpy as np
+    import torch
+    import bench
+    rec = torch.full((2, 4, 112), 7.0)
+    for b, rows in enumerate([[(3, 1), (1, 2), (2, 1)], [(5, 5)]]):
+        for i, (ix, iy) in enumerate(rows):
+            rec[b, i, 1], rec[b, i, 2], rec[b, i, 12] = ix, iy, 10 * ix + iy
+    a = bench.decoded_arrays(torch.tensor([3, 1], dtype=torch.int32), rec)
+    assert a["boxes"][0, :3, 1].tolist() == [2, 3, 1] and a["boxes"][0, :3, 2].tolist() == [1, 1, 2]
+    assert a["box_features"][0, :3, 0].tolist() == [21, 31, 12] and a["box_features"].shape == (2, 4, 100)
+    assert not a["boxes"][0, 3:].any() and not a["boxes"][1, 1:].any() and a["boxes"][1, 0, 1] == 5
+    big = np.arange(bench.DUMP_ARRAY_BYTES // 4 + 1000, dtype=np.float32)
+    for d in ("d1", "d2"):
+        bench.dump_outputs(str(tmp_path / d), {**a, "big": big})
+    for name in ("counts", "boxes", "box_features", "big"):
+        x1, x2 = np.load(tmp_path / "d1" / f"{name}.npy"), np.load(tmp_path / "d2" / f"{name}.npy")
+        assert x1.dtype in (np.float32, np.float64) and np.array_equal(x1, x2)
+    s = np.load(tmp_path / "d1" / "big.npy")
+    assert s.nbytes == bench.DUMP_ARRAY_BYTES and np.all(np.diff(s) > 0)
+    assert np.load(tmp_path / "d1" / "counts.npy").dtype == np.float64
+    # the NMS channel's -inf (non-peak) entries: written as 0 beside a 0/1 peak map; any other non-finite output is refused
+    heat = torch.randn(2, 4, 4, 10)
+    heat[..., 1][heat[..., 1] < 0.5] = float("-inf")
+    h = bench.heatmap_arrays(heat)
+    peak = torch.isfinite(heat[..., 1]).numpy()
+    assert np.array_equal(h["nms_peak_mask"], peak.astype(np.float32)) and np.isfinite(h["heatmap"]).all()
+    assert np.array_equal(h["heatmap"][..., 1][peak], heat[..., 1].numpy()[peak]) and not h["heatmap"][..., 1][~peak].any()
+    assert np.array_equal(np.delete(h["heatmap"], 1, axis=3), np.delete(heat.numpy(), 1, axis=3))
+    bench.dump_outputs(str(tmp_path / "d3"), h)
+    with pytest.raises(ValueError, match="non-finite"):
+        bench.dump_outputs(str(tmp_path / "d4"), {"heatmap": heat.numpy()})

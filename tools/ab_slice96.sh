@@ -2,7 +2,7 @@
 # usage (GPU box): tools/ab_slice96.sh -- the 96-channel slices of FTC_OP_MBHEAD (stage 6 at batch 8: 256 instead of 192 workgroups) against 128 everywhere
 OUT=gpurun_out/r5j; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_ops.py tests/test_gpu_train_ops.py -q -x -k "mbconv_slice or train_mode_forward" 2>&1 | tail -8
-B="python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-fp32 --no-sustained --no-seam2 --no-configs"
+B="python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-fp32 --no-sustained --no-seam2 --no-configs"
 $B --dump-ops $OUT/ops_96.json > $OUT/b96.json 2> $OUT/b96.err
 FTC_MBSLICE_96=0 $B --dump-ops $OUT/ops_128.json > $OUT/b128.json 2> $OUT/b128.err
 $B > $OUT/b96b.json 2>/dev/null

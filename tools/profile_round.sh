@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 # --lanes 1: the profiled passes run the steps on ONE stream, so that a kernel's duration is its own (two lanes co-schedule kernels of two
 # batches) and the launch order maps onto the plan's ops (profiles/pmc_kernels.py)
 CMD="python bench.py --steps 3 --warmup 2 --lanes 1 --no-cpu-baseline --no-fp32 --no-profile --no-sustained --no-seam2 --no-configs"
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp32 --no-sustained --no-seam2 --no-configs --dump-ops "$OUT/ops.json" > "$OUT/bench_unprofiled.json" 2> "$OUT/bench_unprofiled.err"
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-fp32 --no-sustained --no-seam2 --no-configs --dump-ops "$OUT/ops.json" > "$OUT/bench_unprofiled.json" 2> "$OUT/bench_unprofiled.err"
 rocprofv3 --kernel-trace --stats -d "$OUT" -o trace -- $CMD > "$OUT/trace.log" 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT" -o fetch -- $CMD > "$OUT/fetch.log" 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$OUT" -o write -- $CMD > "$OUT/write.log" 2>&1
