@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libftc_hip.so")
 
-FTC_ABI_VERSION = 10
+FTC_ABI_VERSION = 11
 F32, BF16, F16 = 0, 1, 2
 (BASE_NULL, BASE_WORKSPACE, BASE_WEIGHTS, BASE_INPUT, BASE_HEATMAP, BASE_FEATURES, BASE_GRADS, NUM_BASES) = range(8)
 OP_STEM, OP_CONV, OP_DWCONV, OP_SE, OP_UPCAT, OP_NMS, OP_TAPSUM, OP_BNSTAT, OP_BNACT = 1, 2, 3, 4, 5, 6, 7, 8, 9
@@ -31,6 +31,7 @@ EXPORTS = ["ftc_abi_version", "ftc_last_error", "ftc_device_info", "ftc_plan_cre
            "ftc_create", "ftc_destroy", "ftc_weights_bytes", "ftc_weights_host", "ftc_weights_offset", "ftc_workspace_bytes", "ftc_forward",
            "ftc_model_plan", "ftc_model_op_info", "ftc_plan_op",
            "ftc_topk_mask", "ftc_mask_compact", "ftc_gather_rows", "ftc_decoder_workspace_bytes", "ftc_decoder_forward",
+           "ftc_glyph_select", "ftc_glyph_decode_workspace_bytes", "ftc_glyph_decode",
            "ftc_losses_scratch_bytes", "ftc_losses", "ftc_cov_weighting_step", "ftc_pack_train_weights", "ftc_wgrad_splits"]
 
 
@@ -142,6 +143,10 @@ def load():
     lib.ftc_decoder_workspace_bytes.argtypes = [vp, i32]
     lib.ftc_decoder_workspace_bytes.restype = i64
     lib.ftc_decoder_forward.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.ftc_glyph_select.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, vp, vp, vp]
+    lib.ftc_glyph_decode_workspace_bytes.argtypes = [vp, i32]
+    lib.ftc_glyph_decode_workspace_bytes.restype = i64
+    lib.ftc_glyph_decode.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.ftc_losses_scratch_bytes.restype = i64
     lib.ftc_losses.argtypes = [vp, C.POINTER(i64), vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp]
     lib.ftc_cov_weighting_step.argtypes = [vp, i32, i32, vp, vp, vp]

@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "conv_igemm_impl.h"
+#include "ftc_host.h"
 
 using namespace convimpl;
 
@@ -120,6 +121,19 @@ const char* conv_validate(const ftc_op& op) {
     if (hint_bk(op) == 128 && !ftc_is16(op.in_dtype)) return "conv: K step 128 needs 16-bit activations";
     if (hint_stage(op) >= 2 && !glds_legal(op)) return "conv: direct-to-LDS kernel is not legal for this op/tile";
     return nullptr;
+}
+
+// The kernel choice `op` runs with, written out in aux0 (tile config, staging, K step; the halo bits kept) so that it no longer
+// depends on the pixel count through the default heuristics.  Split-K and the 144-pixel tiles sum in another order or need a pixel count
+// that is a multiple of 144: they are replaced (no split-K; the 128-channel default tile of a large map).
+int conv_pinned_choice(const ftc_op& op) {
+    int cfg = select_cfg(op);
+    if (cfg_px144(cfg)) cfg = default_cfg(op.Cout, 1 << 24);
+    ftc_op t = op;
+    t.aux0 = (op.aux0 & 0x3f0) | (cfg + 1);
+    const int stage = uses_glds(t) ? glds_ring(t) : 1;
+    const int bk = select_bk(t);
+    return (op.aux0 & 0xc0) | (cfg + 1) | (stage << 4) | ((bk == 32 ? 1 : bk == 64 ? 2 : 3) << 8);
 }
 
 hipError_t launch_conv(const OpArgs& a, hipStream_t s) {

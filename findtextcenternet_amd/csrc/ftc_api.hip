@@ -585,6 +585,17 @@ int ftc_plan_profile(const ftc_plan* plan, void* const bases[FTC_NUM_BASES], voi
     return ret;
 }
 
+int ftc_glyph_select(const float* logits0, const float* logits1, const float* logits2, int64_t ld0, int64_t ld1, int64_t ld2, int n,
+                     float* soft0, float* soft1, float* soft2, int64_t* ids, float* probs, void* stream) {
+    if (n < 0) return fail(FTC_ERR_INVALID, "ftc_glyph_select: n < 0");
+    if (ld0 < 1091 || ld1 < 1093 || ld2 < 1097) return fail(FTC_ERR_INVALID, "ftc_glyph_select: row pitch ld_k must be >= m_k (1091, 1093, 1097)");
+    if (n == 0) return FTC_OK;
+    if (!logits0 || !logits1 || !logits2 || !ids || !probs) return fail(FTC_ERR_INVALID, "ftc_glyph_select: null pointer argument");
+    hipError_t e = ftc_glyph_select_launch(logits0, logits1, logits2, ld0, ld1, ld2, n, soft0, soft1, soft2, ids, probs, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail_hip(e, "ftc_glyph_select");
+    return FTC_OK;
+}
+
 int ftc_decode(const float* heatmap, const float* features, int B, int h, int w, int C, const ftc_tile* tiles_dev,
                float logit_cut, int scale, int max_boxes, float* boxes, int box_stride, float* feats, int feat_stride,
                int32_t* index, int32_t* counts, void* scratch_dev, void* stream) {

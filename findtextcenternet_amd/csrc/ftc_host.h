@@ -1,5 +1,7 @@
 // Host-side definitions shared by the C-ABI translation units (ftc_api.hip, model.hip).
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -26,3 +28,9 @@ bool ftc_fmbconv_legal(const ftc_op& o);
 
 // conv_igemm.hip: NULL if the convolution op (incl. its tuned kernel choice ftc_op.aux0) is supported, else the reason
 const char* conv_validate(const ftc_op& op);
+
+// glyph_select.hip: the per-glyph code-point selection kernel behind ftc_glyph_select / ftc_glyph_decode (arguments validated by the caller)
+hipError_t ftc_glyph_select_launch(const float* l0, const float* l1, const float* l2, int64_t ld0, int64_t ld1, int64_t ld2, int n,
+                                   float* s0, float* s1, float* s2, int64_t* ids, float* probs, hipStream_t stream);
+// conv_igemm.hip: aux0 with the kernel choice the op would run with made explicit (tile config, staging, K step), split-K dropped
+int conv_pinned_choice(const ftc_op& op);

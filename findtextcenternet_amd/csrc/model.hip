@@ -303,6 +303,12 @@ struct ftc_model {
     std::map<int, uint64_t> decoder_plan_use;
     uint64_t decoder_clock = 0;
     static constexpr size_t kMaxDecoderPlans = 16;
+    // ftc_glyph_decode: decoder plans by row BUCKET, every one running the GEMM kernel choices of `glyph_pins` (one aux0 per op, taken
+    // from the plan of kGlyphPinRows rows) -- a row's logits then do not depend on the batch it came in.  Same LRU bound.
+    std::map<int, std::shared_ptr<ModelPlan>> glyph_plans;
+    std::map<int, uint64_t> glyph_plan_use;
+    std::vector<int> glyph_pins;
+    static constexpr int kGlyphPinRows = 8192;
 };
 
 namespace {
@@ -1208,35 +1214,71 @@ int ftc_forward(ftc_model* model, const void* weights_dev, const void* image, in
     return ftc_plan_run(&mp->plan, bases, stream, 0, with_nms ? n - 1 : n - 2);
 }
 
-static int get_decoder_plan(ftc_model* m, int n_rows, std::shared_ptr<ModelPlan>* out) {
+static int get_decoder_plan(ftc_model* m, int n_rows, std::shared_ptr<ModelPlan>* out, bool glyph = false) {
     if (!m) return ftc_set_error(FTC_ERR_INVALID, "ftc decoder: null model");
     if (!m->has_decoder) return ftc_set_error(FTC_ERR_INVALID, "ftc decoder: the model was created from a checkpoint without decoder.* tensors");
     if (n_rows <= 0) return ftc_set_error(FTC_ERR_INVALID, "ftc decoder: n_rows must be positive");
     std::lock_guard<std::mutex> lk(m->mu);
-    auto it = m->decoder_plans.find(n_rows);
-    if (it == m->decoder_plans.end()) {
+    auto& plans = glyph ? m->glyph_plans : m->decoder_plans;
+    auto& use = glyph ? m->glyph_plan_use : m->decoder_plan_use;
+    if (glyph && m->glyph_pins.empty()) {
+        ModelPlan ref;
+        Builder b(m, 1, ftc_model::kGlyphPinRows, 1, false);
+        int rc = b.build_decoder(&ref);
+        if (rc != FTC_OK) return rc;
+        for (const ftc_op& o : ref.plan.ops) m->glyph_pins.push_back(o.kind == FTC_OP_CONV ? conv_pinned_choice(o) : o.aux0);
+    }
+    auto it = plans.find(n_rows);
+    if (it == plans.end()) {
         std::shared_ptr<ModelPlan> mp(new (std::nothrow) ModelPlan());
         if (!mp) return ftc_set_error(FTC_ERR_NOMEM, "ftc decoder: out of host memory");
-        if (m->decoder_plans.size() >= ftc_model::kMaxDecoderPlans) {
-            auto lru = m->decoder_plan_use.begin();
-            for (auto u = m->decoder_plan_use.begin(); u != m->decoder_plan_use.end(); ++u)
+        if (plans.size() >= ftc_model::kMaxDecoderPlans) {
+            auto lru = use.begin();
+            for (auto u = use.begin(); u != use.end(); ++u)
                 if (u->second < lru->second) lru = u;
-            m->decoder_plans.erase(lru->first);
-            m->decoder_plan_use.erase(lru);
+            plans.erase(lru->first);
+            use.erase(lru);
         }
         Builder b(m, 1, n_rows, 1, false);
         int rc = b.build_decoder(mp.get());
         if (rc != FTC_OK) return rc;
+        if (glyph) {
+            if (mp->plan.ops.size() != m->glyph_pins.size()) return ftc_set_error(FTC_ERR_INVALID, "ftc glyph decode: decoder plans differ in length");
+            for (size_t i = 0; i < mp->plan.ops.size(); ++i) mp->plan.ops[i].aux0 = m->glyph_pins[i];
+        }
         ftc_plan* checked = nullptr;
         rc = ftc_plan_create(mp->plan.ops.data(), (int)mp->plan.ops.size(), mp->plan.workspace_bytes, mp->plan.weights_bytes, &checked);
         if (rc != FTC_OK) return rc;
         ftc_plan_destroy(checked);
-        it = m->decoder_plans.emplace(n_rows, std::move(mp)).first;
+        it = plans.emplace(n_rows, std::move(mp)).first;
     }
-    m->decoder_plan_use[n_rows] = ++m->decoder_clock;
+    use[n_rows] = ++m->decoder_clock;
     *out = it->second;
     return FTC_OK;
 }
+
+// ftc_glyph_decode pads the batch to 64 * 2^k or 96 * 2^k rows (at most 1.5x the work of the rows themselves)
+static int64_t glyph_bucket(int n) {
+    for (int64_t b = 64;; b *= 2) {
+        if (n <= b) return b;
+        if (n <= b * 3 / 2) return b * 3 / 2;
+    }
+}
+
+namespace {
+constexpr int kGlyphMod[3] = {1091, 1093, 1097};          // util_func.py:5 modulo_list
+int64_t align256(int64_t v) { return (v + 255) & ~int64_t(255); }
+struct GlyphLayout { int64_t rows, logits[3], plan, total; };
+GlyphLayout glyph_layout(const ftc_model* m, int64_t bucket, int64_t plan_ws) {
+    GlyphLayout g;
+    int64_t off = 0;
+    g.rows = off; off += align256(bucket * 128 * (m->precision == FTC_F32 ? 4 : 2));
+    for (int k = 0; k < 3; ++k) { g.logits[k] = off; off += align256(bucket * kGlyphMod[k] * 4); }
+    g.plan = off; off += align256(plan_ws);
+    g.total = off;
+    return g;
+}
+}  // namespace
 
 int64_t ftc_decoder_workspace_bytes(ftc_model* model, int n_rows) {
     std::shared_ptr<ModelPlan> mp;
@@ -1256,6 +1298,48 @@ int ftc_decoder_forward(ftc_model* model, const void* weights_dev, const void* r
         rc = ftc_plan_run(&mp->plan, bases, stream, 3 * i, 3 * i + 2);
         if (rc != FTC_OK) return rc;
     }
+    return FTC_OK;
+}
+
+int64_t ftc_glyph_decode_workspace_bytes(ftc_model* model, int n_rows) {
+    if (n_rows < 0) { ftc_set_error(FTC_ERR_INVALID, "ftc_glyph_decode_workspace_bytes: n_rows < 0"); return -1; }
+    if (n_rows == 0) return 0;
+    if (n_rows > (1 << 24)) { ftc_set_error(FTC_ERR_INVALID, "ftc_glyph_decode_workspace_bytes: more than 2^24 rows (split the batch)"); return -1; }
+    const int64_t bucket = glyph_bucket(n_rows);
+    std::shared_ptr<ModelPlan> mp;
+    if (get_decoder_plan(model, (int)bucket, &mp, true) != FTC_OK) return -1;
+    return glyph_layout(model, bucket, mp->plan.workspace_bytes).total;
+}
+
+int ftc_glyph_decode(ftc_model* model, const void* weights_dev, const void* rows, int n_rows, int64_t* ids, float* probs,
+                     float* soft0, float* soft1, float* soft2, void* workspace, void* stream) {
+    if (!model) return ftc_set_error(FTC_ERR_INVALID, "ftc_glyph_decode: null model");
+    if (n_rows < 0) return ftc_set_error(FTC_ERR_INVALID, "ftc_glyph_decode: n_rows < 0");
+    if (n_rows > (1 << 24)) return ftc_set_error(FTC_ERR_INVALID, "ftc_glyph_decode: more than 2^24 rows (split the batch)");
+    if (!model->has_decoder) return ftc_set_error(FTC_ERR_INVALID, "ftc decoder: the model was created from a checkpoint without decoder.* tensors");
+    if (n_rows == 0) return FTC_OK;
+    if (!weights_dev || !rows || !ids || !probs || !workspace) return ftc_set_error(FTC_ERR_INVALID, "ftc_glyph_decode: null pointer argument");
+    const int64_t bucket = glyph_bucket(n_rows);
+    std::shared_ptr<ModelPlan> mp;
+    int rc = get_decoder_plan(model, (int)bucket, &mp, true);
+    if (rc != FTC_OK) return rc;
+    const GlyphLayout g = glyph_layout(model, bucket, mp->plan.workspace_bytes);
+    char* ws = static_cast<char*>(workspace);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // the bucket's rows: the caller's n_rows, zeros after them (the plan reads `bucket` rows)
+    const int64_t row_bytes = 128 * (model->precision == FTC_F32 ? 4 : 2);
+    hipError_t e = hipMemcpyAsync(ws + g.rows, rows, (size_t)(n_rows * row_bytes), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && bucket > n_rows) e = hipMemsetAsync(ws + g.rows + n_rows * row_bytes, 0, (size_t)((bucket - n_rows) * row_bytes), s);
+    if (e != hipSuccess) return ftc_set_error(FTC_ERR_HIP, std::string("ftc_glyph_decode: ") + hipGetErrorString(e));
+    for (int i = 0; i < 3; ++i) {
+        void* bases[FTC_NUM_BASES] = {nullptr, ws + g.plan, const_cast<void*>(weights_dev), ws + g.rows, ws + g.logits[i], nullptr};
+        rc = ftc_plan_run(&mp->plan, bases, stream, 3 * i, 3 * i + 2);
+        if (rc != FTC_OK) return rc;
+    }
+    e = ftc_glyph_select_launch(reinterpret_cast<const float*>(ws + g.logits[0]), reinterpret_cast<const float*>(ws + g.logits[1]),
+                                reinterpret_cast<const float*>(ws + g.logits[2]), kGlyphMod[0], kGlyphMod[1], kGlyphMod[2], n_rows,
+                                soft0, soft1, soft2, ids, probs, s);
+    if (e != hipSuccess) return ftc_set_error(FTC_ERR_HIP, std::string("ftc_glyph_decode: select launch: ") + hipGetErrorString(e));
     return FTC_OK;
 }
 

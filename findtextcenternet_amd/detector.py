@@ -349,6 +349,37 @@ class SimpleDecoder(nn.Module):
         return owner._decode_rows(x)
 
 
+class CodeDecoder(nn.Module):
+    """models/detector.py:298-305: ``SimpleDecoder`` followed by a softmax over each CRT head.  Wraps the ``SimpleDecoder`` of a
+    ``TextDetectorModel`` (state_dict keys ``decoder.blocks.<i>...`` as the reference's).  Eval-only and GPU-only: ``forward(x[N,100])``
+    runs ``ftc_glyph_decode`` (decoder GEMMs + the softmax of csrc/glyph_select.hip) and returns the three softmax tensors [N, m_k] fp32;
+    a row's values do not depend on the batch it came in.  ``.to()`` records the device only: the weights that run are the owner's packed
+    blob, which moving the wrapped parameters would force to be re-packed."""
+
+    def __init__(self, decoder, *args, **kwargs) -> None:
+        super().__init__(*args, **kwargs)
+        if not isinstance(decoder, SimpleDecoder):
+            raise TypeError("CodeDecoder expects a findtextcenternet_amd SimpleDecoder (TextDetectorModel.decoder)")
+        self.decoder = decoder
+        self._device = None
+
+    def to(self, *args, **kwargs):
+        device = torch._C._nn._parse_to(*args, **kwargs)[0]
+        if device is not None:
+            self._device = torch.device(device)
+        return self
+
+    def forward(self, x):
+        owner = self.decoder.__dict__.get("_owner")
+        if owner is None:
+            raise NotImplementedError("SimpleDecoder runs as part of a TextDetectorModel (it shares the model's packed weight blob)")
+        if self.training:
+            raise NotImplementedError("findtextcenternet_amd implements the eval-mode forward only; call .eval()")
+        from .glyphs import glyph_decode_device
+        _, _, softs = glyph_decode_device(owner, x, with_softmax=True)
+        return tuple(softs)
+
+
 class TextDetectorModel(nn.Module):
     """models/detector.py:256-281.  ``forward(x, fmask)`` and ``get_fmask`` implement the reference's eval-mode (validation) step
     on the GPU; training-mode forward (batch-statistics BatchNorm, stochastic depth) and backward are not implemented."""

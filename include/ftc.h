@@ -40,8 +40,9 @@ extern "C" {
    8: ftc_page_order, page_h / page_w arguments of ftc_page_merge (parallel page-level selection); FTC_FLAG_SE_INLINE
    9: FTC_FLAG_SE_INLINE removed (flag bit 0x20000000 is free again); FTC_MBHEAD_MAX_SQUEEZE; KBLOCK32 validation on CONV;
       ftc_page_merge_variant (the demo script's selection + two-pass seed rows)
-   10: FTC_OP_FMBCONV (Fused-MBConv block with expansion in one launch: 3x3 expand + SiLU + 1x1 project + residual) */
-#define FTC_ABI_VERSION 10
+   10: FTC_OP_FMBCONV (Fused-MBConv block with expansion in one launch: 3x3 expand + SiLU + 1x1 project + residual)
+   11: glyph code-point decode: ftc_glyph_select, ftc_glyph_decode_workspace_bytes, ftc_glyph_decode */
+#define FTC_ABI_VERSION 11
 
 typedef enum ftc_status {
     FTC_OK = 0,
@@ -511,6 +512,29 @@ int ftc_gather_rows(const float* features, const int32_t* sel_index, const int32
 int64_t ftc_decoder_workspace_bytes(ftc_model* model, int n_rows);
 int ftc_decoder_forward(ftc_model* model, const void* weights_dev, const void* rows, int n_rows, float* out0, float* out1, float* out2,
                         void* workspace, void* stream);
+/* Glyph code points (CodeDecoder, models/detector.py:298-305, + the demo's host routine decode(), test_image1_torch.py:267-298 =
+   fine_image/process_image1_torch.py:300-330; calc_predid = util_func.py:92-126).  Per glyph i:
+     1. softmax of each head's logits;
+     2. per head the candidates = the indices with p > 0.01 in ascending order, the first three only; none -> the argmax (first index
+        on a tie);
+     3. every combination of candidates (head 0 outermost, at most 27) gets p = exp(mean(log p_k)) (float32, ((l0 + l1) + l2) / 3) and
+        the code point x = CRT(r0, r1, r2) modulo 1091 * 1093 * 1097;
+     4. ids[i] / probs[i] = the combination of largest p among those with x <= 0x10FFFF, the earliest one on a tie; if no combination is
+        valid, the first combination with its own p.
+   logits_k [n, m_k] fp32 with row pitch ld_k >= m_k (m = 1091, 1093, 1097); soft_k [n, m_k] fp32 packed, the softmax rows
+   (CodeDecoder.forward's output), each may be NULL; ids int64 [n], probs fp32 [n].  One wave64 per glyph (csrc/glyph_select.hip).
+   n == 0 is a no-op. */
+int ftc_glyph_select(const float* logits0, const float* logits1, const float* logits2, int64_t ld0, int64_t ld1, int64_t ld2, int n,
+                     float* soft0, float* soft1, float* soft2, int64_t* ids, float* probs, void* stream);
+/* The decoder (as ftc_decoder_forward) and then ftc_glyph_select on its logits, with no host synchronisation and no allocation:
+   rows [n_rows, 128] in the model's compute dtype (as for ftc_decoder_forward); the logits live in the workspace.  Results do not
+   depend on the batch: n_rows is padded up to a bucket (64, 96, 128, 192, 256, 384, ...: 64 * 2^k and 96 * 2^k) and the bucket's
+   decoder plan pins one GEMM configuration (tile shape, staging, K step; no split-K), the same for every bucket, so row i of a batch
+   is bitwise the row decoded alone.  Those plans are cached apart from ftc_decoder_forward's, whose numerics are unchanged.
+   workspace >= ftc_glyph_decode_workspace_bytes(model, n_rows) bytes (-1 on error). */
+int64_t ftc_glyph_decode_workspace_bytes(ftc_model* model, int n_rows);
+int ftc_glyph_decode(ftc_model* model, const void* weights_dev, const void* rows, int n_rows, int64_t* ids, float* probs,
+                     float* soft0, float* soft1, float* soft2, void* workspace, void* stream);
 /* loss_function (loss_func.py:94-177, heatmap_loss :74-92).  heatmap = the NINE reference channels addressed through element strides
    (batch, channel, y, x) so that NHWC and NCHW memory are both accepted; labelmap [B,5,h,w] fp32 and idmap [B,2,h,w] int32 contiguous;
    dec0..2 [cap, 1091 | 1093 | 1097] fp32 decoder outputs of the pixels sel_index[0..count) (may all be NULL: id_loss = 0).
