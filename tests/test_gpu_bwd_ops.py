@@ -137,7 +137,7 @@ def test_wgrad(case, wd, io):
     F.conv2d(round16(xe, wd).permute(0, 3, 1, 2), w, None, stride, pad).backward(round16(dz, wd).permute(0, 3, 1, 2))
     lib = L.load()
     S = int(lib.ftc_wgrad_splits(B, Ho, Wo, Cout, Cin, k))
-    if case[0].startswith("se_image_splits"):                  # (what TrainStep._G.wgrad asks for when the input is gated)
+    if case[0].startswith("se_image_splits"):                  # (what train_graph.Builder.wgrad asks for when the input is gated)
         S = B * (2 if (Ho * Wo) % 128 == 0 and case[0].endswith("slices") is False else 1)
         assert (Ho * Wo) % (S // B * 64) == 0
     pre = torch.randn(Cout, Cin, k, k, generator=g)

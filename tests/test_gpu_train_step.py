@@ -155,7 +155,7 @@ def test_train_step_16bit_gradients_point_the_same_way(g10, precision, cos_min, 
     reference's fp32 gradients.  Measured on this 100-block random-init network (batch statistics over as few as 128 samples):
     fp16 cosine >= 0.990 everywhere (median 0.999); bf16 0.61 - 0.99 (10th percentile 0.64, median 0.93; the heads' last level 0.975+, the
     backbone 0.61 - 0.8: eight times the operand rounding of fp16 accumulated through 100 blocks of backward -- the same factor the
-    inference path shows).  (End of round 3, tools/z16_experiment.py; the median rose from 0.83 when the SE gate of the
+    inference path shows).  (End of round 3; the median rose from 0.83 when the SE gate of the
     project convolutions' weight gradients moved from the staged bf16 elements to the fp32 partial tile.)  The gates sit just below the
     measurement so that a regression in either mode fails."""
     B, H, W = 2, 256, 256
