@@ -34,6 +34,13 @@ EXPORTS = ["ftc_abi_version", "ftc_last_error", "ftc_device_info", "ftc_plan_cre
            "ftc_glyph_select", "ftc_glyph_decode_workspace_bytes", "ftc_glyph_decode",
            "ftc_losses_scratch_bytes", "ftc_losses", "ftc_cov_weighting_step", "ftc_pack_train_weights", "ftc_wgrad_splits"]
 
+# include/ftc_text.h (the text recognizer): its own version and its own list; FTC_ABI_VERSION and EXPORTS above describe include/ftc.h only
+FTC_TEXT_ABI_VERSION = 1
+TEXT_LEN, TEXT_PASSES, TEXT_MASK_TOKEN, TEXT_MAX_BATCH, TEXT_NO_READBACK = 400, 8, 3, 64, 1
+TEXT_EXPORTS = ["ftc_text_abi_version", "ftc_text_create", "ftc_text_destroy", "ftc_text_weights_bytes", "ftc_text_weights_host",
+                "ftc_text_workspace_bytes", "ftc_text_launch_count", "ftc_text_encode", "ftc_text_decode_step", "ftc_text_predict",
+                "ftc_text_attention", "ftc_text_rownorm", "ftc_text_swiglu", "ftc_text_select", "ftc_text_select_host", "ftc_text_row_update"]
+
 
 class FtcLibraryError(RuntimeError):
     pass
@@ -74,6 +81,11 @@ class MtChunk(C.Structure):
 class PackEntry(C.Structure):
     _fields_ = [("src", C.c_void_p), ("fwd", C.c_void_p), ("dgrad", C.c_void_p)] + [
         (n, C.c_int32) for n in ("Cout", "Cin", "kk", "cin_pad", "cout_pad", "dtype", "reserved0", "reserved1")]
+
+
+class TextDims(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("enc_input_dim", "embed_dim", "head_num", "enc_block_num", "dec_block_num", "max_enc_seq_len",
+                                         "max_dec_seq_len", "reserved")]
 
 
 class Tile(C.Structure):
@@ -152,6 +164,28 @@ def load():
     lib.ftc_cov_weighting_step.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.ftc_pack_train_weights.argtypes = [vp, i32, i64, vp]
     lib.ftc_wgrad_splits.argtypes = [i32] * 6
+    lib.ftc_text_abi_version.restype = i32
+    lib.ftc_text_create.argtypes = [C.POINTER(Tensor), i32, C.POINTER(TextDims), i32, C.POINTER(vp)]
+    lib.ftc_text_destroy.argtypes = [vp]
+    lib.ftc_text_destroy.restype = None
+    lib.ftc_text_weights_bytes.argtypes = [vp]
+    lib.ftc_text_weights_bytes.restype = i64
+    lib.ftc_text_weights_host.argtypes = [vp]
+    lib.ftc_text_weights_host.restype = vp
+    lib.ftc_text_workspace_bytes.argtypes = [vp, i32]
+    lib.ftc_text_workspace_bytes.restype = i64
+    lib.ftc_text_launch_count.argtypes = [vp, i32]
+    lib.ftc_text_encode.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
+    lib.ftc_text_decode_step.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.ftc_text_predict.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, C.POINTER(i32), vp, vp]
+    lib.ftc_text_attention.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, vp]
+    lib.ftc_text_rownorm.argtypes = [vp] * 12 + [i64, i32, i32, vp]
+    lib.ftc_text_swiglu.argtypes = [vp, vp, i64, i32, vp]
+    lib.ftc_text_select.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp]
+    lib.ftc_text_select_host.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]
+    lib.ftc_text_row_update.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    if lib.ftc_text_abi_version() != FTC_TEXT_ABI_VERSION:
+        raise FtcLibraryError(f"text ABI mismatch: library {lib.ftc_text_abi_version()} vs binding {FTC_TEXT_ABI_VERSION}")
     if lib.ftc_abi_version() != FTC_ABI_VERSION:
         raise FtcLibraryError(f"ABI mismatch: library {lib.ftc_abi_version()} vs binding {FTC_ABI_VERSION}")
     _lib = lib

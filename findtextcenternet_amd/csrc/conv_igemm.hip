@@ -136,6 +136,8 @@ int conv_pinned_choice(const ftc_op& op) {
     return (op.aux0 & 0xc0) | (cfg + 1) | (stage << 4) | ((bk == 32 ? 1 : bk == 64 ? 2 : 3) << 8);
 }
 
+int conv_small_tile_choice() { return CFG_64x64 + 1; }
+
 hipError_t launch_conv(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
     if (ftc_thin_conv_legal(o)) return launch_thin_conv(a, s);

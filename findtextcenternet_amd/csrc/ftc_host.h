@@ -34,3 +34,6 @@ hipError_t ftc_glyph_select_launch(const float* l0, const float* l1, const float
                                    float* s0, float* s1, float* s2, int64_t* ids, float* probs, hipStream_t stream);
 // conv_igemm.hip: aux0 with the kernel choice the op would run with made explicit (tile config, staging, K step), split-K dropped
 int conv_pinned_choice(const ftc_op& op);
+// conv_igemm.hip: the aux0 of the 64-channel x 64-pixel tile with everything else left to the heuristics (a GEMM with few rows fills more
+// CUs with it)
+int conv_small_tile_choice();

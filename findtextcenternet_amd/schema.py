@@ -173,3 +173,71 @@ def text_detector_schema(model_size: str = "xl") -> "OrderedDict[str, Tuple[Tupl
     for k, v in decoder_schema().items():
         d["decoder." + k] = v
     return d
+
+
+# ---- text recognizer (models/transformer.py; const.py) -------------------------------------------------------------------------
+encoder_add_dim = 6                          # const.py:1-7 (vertical, ruby base, ruby text, space, emphasis, newline)
+encoder_dim = feature_dim + encoder_add_dim
+max_encoderlen = 400
+max_decoderlen = 400
+decoder_PAD, decoder_SOT, decoder_EOT, decoder_MSK = 0, 1, 2, 3
+TEXT_MAX_CODE = 0x3FFFF                      # the mask-predict loop's validity bound (models/transformer.py:332)
+TEXT_ITERATIONS = 8                          # rep_count
+
+
+@dataclass
+class ModelDimensions:
+    """The reference's dataclass of the same name (models/transformer.py:247-256), same fields and defaults."""
+    enc_input_dim: int = encoder_dim
+    embed_dim: int = 768
+    head_num: int = 12
+    enc_block_num: int = 10
+    dec_block_num: int = 10
+    max_enc_seq_len: int = max_encoderlen
+    max_dec_seq_len: int = max_decoderlen
+    dropout: float = 0.0
+
+
+def transformer_schema(dims: "ModelDimensions" = None) -> "OrderedDict[str, Tuple[Tuple[int, ...], str]]":
+    """name -> (shape, kind) of ``Transformer.state_dict()`` in the reference's key order (416 keys for the default dimensions).
+    The ``pos_emb*.encoding`` tables are parameters there, so they are part of a checkpoint."""
+    dims = dims or ModelDimensions()
+    E, d = dims.embed_dim, OrderedDict()
+
+    def attn(p, n):
+        for q in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            d[f"{p}.{q}.weight"] = ((E, E), "t_linear")
+        d[f"{p}.pos_emb_q.encoding"] = ((n, E), "posenc")
+        d[f"{p}.pos_emb_k.encoding"] = ((n, E), "posenc")
+
+    def norm(p):
+        d[f"{p}.weight"] = ((E,), "ln_weight")
+        d[f"{p}.bias"] = ((E,), "ln_bias")
+
+    def ff(p):
+        for q, (o, i) in (("w1", (2 * E, E)), ("wg", (2 * E, E)), ("w2", (E, 2 * E))):
+            d[f"{p}.{q}.weight"] = ((o, i), "t_linear")
+            d[f"{p}.{q}.bias"] = ((o,), "t_bias")
+
+    d["encoder.embed.weight"] = ((E, dims.enc_input_dim), "t_linear")
+    d["encoder.pos_emb.encoding"] = ((dims.max_enc_seq_len, E), "posenc")
+    norm("encoder.norm")
+    for b in range(dims.enc_block_num):
+        p = f"encoder.blocks.{b}"
+        attn(p + ".mha", dims.max_enc_seq_len)
+        norm(p + ".norm1"); norm(p + ".norm2")
+        ff(p + ".ff")
+    for i, m in enumerate(modulo_list):
+        d[f"decoder.embed.{i}.weight"] = ((m, E), "t_embed")
+    d["decoder.pos_emb.encoding"] = ((dims.max_dec_seq_len, E), "posenc")
+    norm("decoder.norm")
+    for b in range(dims.dec_block_num):
+        p = f"decoder.blocks.{b}"
+        attn(p + ".self_attn", dims.max_dec_seq_len)
+        attn(p + ".cross_attn", dims.max_dec_seq_len)
+        norm(p + ".norm1"); norm(p + ".norm2"); norm(p + ".norm3")
+        ff(p + ".ff")
+    for i, m in enumerate(modulo_list):
+        d[f"decoder.out_layers.{i}.weight"] = ((m, E), "t_out_w")
+        d[f"decoder.out_layers.{i}.bias"] = ((m,), "t_out_b")
+    return d

@@ -179,3 +179,70 @@ def load_tf_efficientnetv2_npz(detection_module, weight_path: str, model_size: s
             sd[key] = t.permute(*perm).contiguous() if perm is not None else t
     detection_module.load_state_dict(sd)
     return True
+
+
+# ---- text recognizer ------------------------------------------------------------------------------------------------------------
+TEXT_CODE_BASE, TEXT_CODE_STEP = 0x3041, 7          # code table of the structured output heads: c_j = 0x3041 + 7 j
+TEXT_PLANTED_INVALID = (5, 0x40000 + 12345)         # (column j, code point above 0x3FFFF planted there)
+
+
+def text_code_table(embed_dim: int) -> np.ndarray:
+    """The ``embed_dim`` code points the structured output heads of ``recognizer_state_dict`` can emit (column j -> c_j); one of them
+    lies above 0x3FFFF so that a position's best-scoring candidate can be an invalid code."""
+    c = TEXT_CODE_BASE + TEXT_CODE_STEP * np.arange(embed_dim, dtype=np.int64)
+    if embed_dim > TEXT_PLANTED_INVALID[0]:
+        c[TEXT_PLANTED_INVALID[0]] = TEXT_PLANTED_INVALID[1]
+    return c
+
+
+def sinusoid_table(n: int, d_model: int) -> torch.Tensor:
+    """PositionalEncoding's initial table (models/transformer.py:17-44), float32 as the reference computes it."""
+    pos = torch.arange(0, n).float().unsqueeze(1)
+    two_i = torch.arange(0, d_model, step=2).float()
+    enc = torch.zeros(n, d_model)
+    enc[:, 0::2] = torch.sin(pos / (10000 ** (two_i / d_model)))
+    enc[:, 1::2] = torch.cos(pos / (10000 ** (two_i / d_model)))
+    return enc
+
+
+def recognizer_state_dict(seed: int = 0, dims=None, gain: float = 32.0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded ``Transformer.state_dict()`` (the reference's 416 keys) with STRUCTURED output heads.
+
+    With plain random weights the mask-predict loop is degenerate (no position reaches 0.9, nearly every candidate code is invalid, all
+    eight iterations are identical).  Here the three ``out_layers`` are built from a code table: weight[c_j % m_i, j] = ``gain``, bias 0,
+    so the heads agree on the code point of the decoder output's largest column and the loop feeds real tokens back.  Everything else is
+    default-style random: Linear weights / biases uniform in +-1/sqrt(fan_in), Embedding tables N(0,1), LayerNorm weights near 1; every
+    position table is the sinusoid plus its own small perturbation (a trained checkpoint has moved them apart, and a kernel that picks
+    the wrong table must not pass)."""
+    from .schema import ModelDimensions, modulo_list, transformer_schema
+    dims = dims or ModelDimensions()
+    codes = text_code_table(dims.embed_dim)
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    sinus: Dict[int, torch.Tensor] = {}
+    for name, (shape, kind) in transformer_schema(dims).items():
+        g = _rng(seed, "text." + name)
+        if kind == "t_linear":
+            a = (g.random(shape, dtype=np.float32) * 2 - 1) * np.float32(1.0 / np.sqrt(shape[1]))
+        elif kind == "t_bias":
+            fan_in = {2 * dims.embed_dim: dims.embed_dim, dims.embed_dim: 2 * dims.embed_dim}[shape[0]]
+            a = (g.random(shape, dtype=np.float32) * 2 - 1) * np.float32(1.0 / np.sqrt(fan_in))
+        elif kind == "t_embed":
+            a = g.standard_normal(shape, dtype=np.float32)
+        elif kind == "ln_weight":
+            a = g.uniform(0.9, 1.1, shape).astype(np.float32)
+        elif kind == "ln_bias":
+            a = g.standard_normal(shape, dtype=np.float32) * np.float32(0.05)
+        elif kind == "posenc":
+            if shape[0] not in sinus:
+                sinus[shape[0]] = sinusoid_table(shape[0], shape[1])
+            a = sinus[shape[0]].numpy() + g.standard_normal(shape, dtype=np.float32) * np.float32(0.02)
+        elif kind == "t_out_w":
+            m = shape[0]
+            a = np.zeros(shape, dtype=np.float32)
+            a[codes % m, np.arange(dims.embed_dim)] = np.float32(gain)
+        elif kind == "t_out_b":
+            a = np.zeros(shape, dtype=np.float32)
+        else:
+            raise KeyError(kind)
+        out[name] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    return out
