@@ -159,8 +159,10 @@ class PageDetector:
         return self._run(lambda lo, hi: x_all[lo:hi], origins, org.shape[:2],
                          lambda: torch.from_numpy(org).to(self.device).float() if org.dtype == np.uint8 else torch.from_numpy(np.asarray(org, np.float32)).to(self.device))
 
-    def detect_page(self, im_u8: np.ndarray):
-        """uint8 RGB page [H,W,3] -> same outputs; pads with white and tiles like call_OCR (:63-76)."""
+    def detect_page(self, im_u8: np.ndarray, return_tensors: bool = False):
+        """uint8 RGB page [H,W,3] -> same outputs; pads with white and tiles like call_OCR (:63-76).  ``return_tensors=True``: the second
+        value is the device tensor [M,100] the page merge produced (the recognizer's input rows are gathered from it on the GPU, see
+        ``ocr.recognize_layout``) instead of its host copy; the other three values are unchanged."""
         lib = L.load()
         h0, w0 = im_u8.shape[:2]
         ph, pw = padded_page_size(h0, w0, self.stepx, self.stepy)
@@ -184,7 +186,7 @@ class PageDetector:
         seeds = None
         if self.twopass and (pw / self.stepx > 2 or ph / self.stepy > 2):
             seeds = self._coarse_pass(im_u8, ph, pw)
-        return self._run(gather, origins, (ph, pw), padded_page, seeds=seeds)
+        return self._run(gather, origins, (ph, pw), padded_page, seeds=seeds, return_tensors=return_tensors)
 
     def _coarse_pass(self, im_u8: np.ndarray, ph: int, pw: int):
         """The first pass of the demo script's two-pass mode (test_image1_torch.py:313-332): the white-padded page shrunk by
@@ -204,7 +206,7 @@ class PageDetector:
         return torch.from_numpy(loc0.astype(np.float32)).to(self.device), torch.from_numpy(gf0).to(self.device), float(s_)
 
     # -- shared ------------------------------------------------------------------------------------
-    def _run(self, get_tiles, origins, page_hw, page_f32, seeds=None, cut_off=None, world1=False):
+    def _run(self, get_tiles, origins, page_hw, page_f32, seeds=None, cut_off=None, world1=False, return_tensors=False):
         """get_tiles(lo, hi) -> [n,768,768,3] fp32 0..1 on the GPU; page_hw = (padded) page size; page_f32() -> the padded fp32 page on the GPU.
         seeds (demo variant) = (locations0 fp32 [K,9] unscaled, glyphfeatures0 [K,C], scale) of a coarse pass; world1: no sharding (the coarse pass)."""
         lib = L.load()
@@ -293,7 +295,7 @@ class PageDetector:
                 # pass of the two-pass mode, whose per-rank results are only equal if the GPUs agree bit for bit.
                 self._row_hint = min(self.max_boxes, (cmax + cmax // 4 + 64) // 64 * 64)
             canv_h = canv[1:3].cpu().numpy()
-            return (loc_d if demo else loc_d.cpu().numpy()), glyph_d.cpu().numpy(), canv_h[0], canv_h[1]
+            return (loc_d if demo else loc_d.cpu().numpy()), (glyph_d if return_tensors else glyph_d.cpu().numpy()), canv_h[0], canv_h[1]
 
 
 def linedetect_request(locations: np.ndarray, lines: np.ndarray, seps: np.ndarray) -> bytes:
