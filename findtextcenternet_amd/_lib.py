@@ -41,6 +41,10 @@ TEXT_EXPORTS = ["ftc_text_abi_version", "ftc_text_create", "ftc_text_destroy", "
                 "ftc_text_workspace_bytes", "ftc_text_launch_count", "ftc_text_encode", "ftc_text_decode_step", "ftc_text_predict",
                 "ftc_text_attention", "ftc_text_rownorm", "ftc_text_swiglu", "ftc_text_select", "ftc_text_select_host", "ftc_text_row_update"]
 
+# include/ftc_text_compact.h (the mask-predict loop over the rows still running): a third surface on the same handle
+FTC_TEXT_COMPACT_ABI_VERSION = 1
+TEXT_COMPACT_EXPORTS = ["ftc_text_compact_abi_version", "ftc_text_predict_compact", "ftc_text_attention_rows"]
+
 
 # include/ftc_ocr.h (page-level OCR glue): again its own version and list
 FTC_OCR_ABI_VERSION = 1
@@ -190,10 +194,15 @@ def load():
     lib.ftc_text_select.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp, vp]
     lib.ftc_text_select_host.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp, vp, vp, vp]
     lib.ftc_text_row_update.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ftc_text_compact_abi_version.restype = i32
+    lib.ftc_text_predict_compact.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32), vp, vp]
+    lib.ftc_text_attention_rows.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i32, vp, i64, i32, i32, i32, i32, vp]
     lib.ftc_ocr_abi_version.restype = i32
     lib.ftc_ocr_assemble.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp, vp]
     if lib.ftc_ocr_abi_version() != FTC_OCR_ABI_VERSION:
         raise FtcLibraryError(f"OCR ABI mismatch: library {lib.ftc_ocr_abi_version()} vs binding {FTC_OCR_ABI_VERSION}")
+    if lib.ftc_text_compact_abi_version() != FTC_TEXT_COMPACT_ABI_VERSION:
+        raise FtcLibraryError(f"compact text ABI mismatch: library {lib.ftc_text_compact_abi_version()} vs binding {FTC_TEXT_COMPACT_ABI_VERSION}")
     if lib.ftc_text_abi_version() != FTC_TEXT_ABI_VERSION:
         raise FtcLibraryError(f"text ABI mismatch: library {lib.ftc_text_abi_version()} vs binding {FTC_TEXT_ABI_VERSION}")
     if lib.ftc_abi_version() != FTC_ABI_VERSION:

@@ -19,6 +19,12 @@
 // The cross-attention keys and values do not depend on the pass: Kc_b = (enc + pos_k_b) . Wk_b^T per block and ONE GEMM for all
 // blocks' values (N = blocks * E), once per call.  Rows of a batch never mix, and a row's bits do not depend on B: every GEMM runs the
 // kernel choice of its B = 1 shape (no split-K, no 144-pixel tiles).
+//
+// include/ftc_text_compact.h: ftc_text_predict_compact runs pass p + 1 over the n rows still running after pass p.  A compact decoder
+// pass is a plan with the WORKSPACE LAYOUT OF B AND THE ROW COUNT OF n, cached under (B, n) and built on first use; slot j of its n x 400
+// activation rows stands for row map[j].  Four places see the map: the token-embedding row kernel (tokens of row map[j]), the
+// cross-attention (K, V and padding of row map[j]), the selection (writes compact codes / scores: it simply runs on n x 400 positions)
+// and the row update (reads slot j, writes tokens / ids / probs / done / traces of row map[j]).
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -31,9 +37,19 @@
 #include "ftc_common.h"
 #include "ftc_host.h"
 #include "../../include/ftc_text.h"
+#include "../../include/ftc_text_compact.h"
 
 hipError_t ftc_text_attention_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad,
                                      float* out, int64_t ldo, int B, int heads, int Sq, int Sk, hipStream_t stream);
+hipError_t ftc_text_attention_rows_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad,
+                                          const int32_t* kv_row, int Bkv, float* out, int64_t ldo, int B, int heads, int Sq, int Sk, hipStream_t stream);
+hipError_t ftc_text_rownorm_rows_launch(const float* a, const float* b, const float* pos_in, const float* gamma, const float* beta, const float* pos_out,
+                                        const int64_t* tokens, const float* e0, const float* e1, const float* e2, const int32_t* tok_row, int tok_rows,
+                                        float* out, float* out_pos, int64_t rows, int S, int E, hipStream_t stream);
+hipError_t ftc_text_row_update_rows_launch(int64_t* tokens, const int64_t* codes, const float* scores, int B, int n, int pass, const int32_t* map,
+                                           int32_t* done, int32_t* active, int64_t* ids, float* probs, int64_t* tr_tokens, int64_t* tr_codes,
+                                           float* tr_probs, hipStream_t stream);
+hipError_t ftc_text_row_map_launch(const int32_t* done, int B, int32_t* map, hipStream_t stream);
 hipError_t ftc_text_rownorm_launch(const float* a, const float* b, const float* pos_in, const float* gamma, const float* beta, const float* pos_out,
                                    const int64_t* tokens, const float* e0, const float* e1, const float* e2, float* out, float* out_pos,
                                    int64_t rows, int S, int E, hipStream_t stream);
@@ -86,7 +102,8 @@ struct Layout {
 };
 
 struct TextPlan {
-    int B = 0;
+    int B = 0;                               // workspace layout
+    int n = 0;                               // rows of the decoder steps: B, or the slots of a compact pass (then enc and kv are empty)
     ftc_plan convs;
     std::vector<Step> enc, kv, dec;
     Layout L;
@@ -100,7 +117,7 @@ struct ftc_text {
     std::vector<uint8_t> blob;
     std::map<std::string, int64_t> off;
     std::mutex mu;
-    std::map<int, std::shared_ptr<TextPlan>> plans;
+    std::map<std::pair<int, int>, std::shared_ptr<TextPlan>> plans;      // (B, 0): the whole call; (B, n): a compact decoder pass
 };
 
 namespace {
@@ -237,9 +254,12 @@ int pack(ftc_text* h, const ftc_tensor* tensors, int n) {
 struct PlanBuilder {
     ftc_text* h;
     TextPlan* P;
-    int B;
+    int B;                                   // the workspace layout is that of B rows
+    int n;                                   // the steps run on n rows; n != B: a compact pass, slot j = row map[j]
     std::string err;
-    int64_t R() const { return (int64_t)B * S; }
+    int64_t R() const { return (int64_t)n * S; }
+    bool compact() const { return n != B; }
+    int64_t map_off() const { return P->L.flags + (int64_t)(FTC_TEXT_MAX_BATCH + FTC_TEXT_PASSES) * 4; }
     int64_t W(const std::string& name) {
         auto it = h->off.find(name);
         if (it == h->off.end()) { if (err.empty()) err = "internal: no packed tensor " + name; return 0; }
@@ -289,21 +309,27 @@ struct PlanBuilder {
         const int64_t g = gb.empty() ? -1 : W(gb + ".g"), be = gb.empty() ? -1 : W(gb + ".b");
         const int64_t e0 = tokens ? W("dec.emb0") : -1, e1 = tokens ? W("dec.emb1") : -1, e2 = tokens ? W("dec.emb2") : -1;
         const int64_t rows = R();
-        const int E = h->d.embed_dim;
+        const int E = h->d.embed_dim, B_ = B;
+        const int64_t map = tokens && compact() ? map_off() : -1;
         return [=](const Ctx& c) {
             auto wsf = [&](int64_t o) { return o < 0 ? nullptr : reinterpret_cast<float*>(c.ws + o); };
             auto wtf = [&](int64_t o) { return o < 0 ? nullptr : reinterpret_cast<const float*>(c.wt + o); };
-            return hip(ftc_text_rownorm_launch(wsf(a), wsf(b), wtf(pos_in), wtf(g), wtf(be), wtf(pos_out), tokens ? c.tokens : nullptr, wtf(e0), wtf(e1),
-                                               wtf(e2), wsf(out), wsf(out_pos), rows, S, E, c.s), "row kernel");
+            return hip(ftc_text_rownorm_rows_launch(wsf(a), wsf(b), wtf(pos_in), wtf(g), wtf(be), wtf(pos_out), tokens ? c.tokens : nullptr, wtf(e0), wtf(e1),
+                                                    wtf(e2), map < 0 ? nullptr : reinterpret_cast<const int32_t*>(c.ws + map), B_, wsf(out), wsf(out_pos),
+                                                    rows, S, E, c.s), "row kernel");
         };
     }
-    Step attention(int64_t q, int ldq, int64_t k, int ldk, int64_t v, int ldv, bool masked, int64_t out) {
-        const int B_ = B, heads = h->d.head_num, E = h->d.embed_dim;
+    // cross: keys, values and padding are per-call state in the B-row layout (a compact pass reads them through the map); otherwise
+    // q, k and v are this pass's own activations, slot by slot
+    Step attention(int64_t q, int ldq, int64_t k, int ldk, int64_t v, int ldv, bool masked, int64_t out, bool cross = false) {
+        const int B_ = B, n_ = n, heads = h->d.head_num, E = h->d.embed_dim;
         const int64_t pad = masked ? P->L.pad : -1;
+        const int64_t map = cross && compact() ? map_off() : -1;
         return [=](const Ctx& c) {
             auto f = [&](int64_t o) { return reinterpret_cast<float*>(c.ws + o); };
-            return hip(ftc_text_attention_launch(f(q), ldq, f(k), ldk, f(v), ldv, pad < 0 ? nullptr : reinterpret_cast<const uint8_t*>(c.ws + pad), f(out), E,
-                                                 B_, heads, S, S, c.s), "attention");
+            return hip(ftc_text_attention_rows_launch(f(q), ldq, f(k), ldk, f(v), ldv, pad < 0 ? nullptr : reinterpret_cast<const uint8_t*>(c.ws + pad),
+                                                      map < 0 ? nullptr : reinterpret_cast<const int32_t*>(c.ws + map), map < 0 ? n_ : B_, f(out), E, n_, heads,
+                                                      S, S, c.s), "attention");
         };
     }
     Step swiglu(int64_t in, int64_t out) {
@@ -317,7 +343,7 @@ struct PlanBuilder {
     int build() {
         const ftc_text_dims& d = h->d;
         const int E = d.embed_dim, NB = d.dec_block_num;
-        const int64_t r = R();
+        const int64_t r = (int64_t)B * S;
         Layout& L = P->L;
         int64_t o = 0;
         auto take = [&](int64_t bytes) { const int64_t at = o; o += al(bytes); return at; };
@@ -326,7 +352,7 @@ struct PlanBuilder {
         L.x1 = take(r * E * 4); L.g = take(r * 4 * E * 4); L.hh = take(r * 2 * E * 4); L.d = take(r * E * 4); L.d2 = take(r * E * 4);
         L.kall = take(r * NB * E * 4); L.vall = take(r * NB * E * 4);
         for (int i = 0; i < 3; ++i) L.logit[i] = take(r * MOD[i] * 4);
-        L.tokens = take(r * 8); L.codes = take(r * 8); L.scores = take(r * 4); L.flags = take((FTC_TEXT_MAX_BATCH + FTC_TEXT_PASSES) * 4);
+        L.tokens = take(r * 8); L.codes = take(r * 8); L.scores = take(r * 4); L.flags = take((FTC_TEXT_MAX_BATCH + FTC_TEXT_PASSES + FTC_TEXT_MAX_BATCH) * 4);      // done, active, map
         L.total = o;
         auto ffn = [&](std::vector<Step>& st, const std::string& t, int64_t x) {          // x -> t0 = ff(x) + x
             st.push_back(gemm(x, E, E, t + ".ff1.w", t + ".ff1.b", 4 * E, L.g, 4 * E, 0));
@@ -339,24 +365,26 @@ struct PlanBuilder {
             st.push_back(attention(L.qkv, 3 * E, L.qkv + (int64_t)E * 4, 3 * E, L.qkv + (int64_t)2 * E * 4, 3 * E, masked, L.att));
             st.push_back(gemm(L.att, E, E, t + ".s.o.w", "zero", E, L.t0, E, 0, x));
         };
-        // ---- encoder
-        P->enc.push_back(gemm(L.xin, KPAD, KPAD, "enc.embed.w", "zero", E, L.t0, E, 0));
-        P->enc.push_back(norm(L.t0, -1, W("enc.pos"), "enc.norm", L.enc, d.enc_block_num ? W("enc.0.s.posq") : -1, d.enc_block_num ? L.xp : -1));
-        for (int b = 0; b < d.enc_block_num; ++b) {
-            const std::string t = "enc." + std::to_string(b);
-            self_attn(P->enc, t, L.enc, true);
-            P->enc.push_back(norm(L.t0, -1, -1, t + ".n1", L.x1, -1, -1));
-            ffn(P->enc, t, L.x1);
-            const bool last = b + 1 == d.enc_block_num;
-            P->enc.push_back(norm(L.t0, L.enc, -1, t + ".n2", L.enc, last ? -1 : W("enc." + std::to_string(b + 1) + ".s.posq"), last ? -1 : L.xp));
+        // ---- encoder, and the cross-attention keys / values once per call (a compact pass finds both in the workspace)
+        if (!compact()) {
+            P->enc.push_back(gemm(L.xin, KPAD, KPAD, "enc.embed.w", "zero", E, L.t0, E, 0));
+            P->enc.push_back(norm(L.t0, -1, W("enc.pos"), "enc.norm", L.enc, d.enc_block_num ? W("enc.0.s.posq") : -1, d.enc_block_num ? L.xp : -1));
+            for (int b = 0; b < d.enc_block_num; ++b) {
+                const std::string t = "enc." + std::to_string(b);
+                self_attn(P->enc, t, L.enc, true);
+                P->enc.push_back(norm(L.t0, -1, -1, t + ".n1", L.x1, -1, -1));
+                ffn(P->enc, t, L.x1);
+                const bool last = b + 1 == d.enc_block_num;
+                P->enc.push_back(norm(L.t0, L.enc, -1, t + ".n2", L.enc, last ? -1 : W("enc." + std::to_string(b + 1) + ".s.posq"), last ? -1 : L.xp));
+            }
+            // ---- cross-attention keys / values
+            for (int b = 0; b < NB; ++b) {
+                const std::string t = "dec." + std::to_string(b);
+                P->kv.push_back(norm(L.enc, -1, -1, "", -1, W(t + ".c.posk"), L.xp));
+                P->kv.push_back(gemm(L.xp, E, E, t + ".c.k.w", "zero", E, L.kall, NB * E, b * E));
+            }
+            if (NB) P->kv.push_back(gemm(L.enc, E, E, "dec.cv.w", "zero", NB * E, L.vall, NB * E, 0));
         }
-        // ---- cross-attention keys / values, once per call
-        for (int b = 0; b < NB; ++b) {
-            const std::string t = "dec." + std::to_string(b);
-            P->kv.push_back(norm(L.enc, -1, -1, "", -1, W(t + ".c.posk"), L.xp));
-            P->kv.push_back(gemm(L.xp, E, E, t + ".c.k.w", "zero", E, L.kall, NB * E, b * E));
-        }
-        if (NB) P->kv.push_back(gemm(L.enc, E, E, "dec.cv.w", "zero", NB * E, L.vall, NB * E, 0));
         // ---- one decoder pass
         P->dec.push_back(norm(-1, -1, W("dec.pos"), "dec.norm", L.d, NB ? W("dec.0.s.posq") : -1, NB ? L.xp : -1, true));
         for (int b = 0; b < NB; ++b) {
@@ -364,7 +392,7 @@ struct PlanBuilder {
             self_attn(P->dec, t, L.d, false);
             P->dec.push_back(norm(L.t0, -1, -1, t + ".n1", L.x1, W(t + ".c.posq"), L.xp));
             P->dec.push_back(gemm(L.xp, E, E, t + ".c.q.w", "zero", E, L.qkv, 3 * E, 0));
-            P->dec.push_back(attention(L.qkv, 3 * E, L.kall + (int64_t)b * E * 4, NB * E, L.vall + (int64_t)b * E * 4, NB * E, true, L.att));
+            P->dec.push_back(attention(L.qkv, 3 * E, L.kall + (int64_t)b * E * 4, NB * E, L.vall + (int64_t)b * E * 4, NB * E, true, L.att, true));
             P->dec.push_back(gemm(L.att, E, E, t + ".c.o.w", "zero", E, L.t0, E, 0, L.x1));
             P->dec.push_back(norm(L.t0, -1, -1, t + ".n2", L.d2, -1, -1));
             ffn(P->dec, t, L.d2);
@@ -386,19 +414,23 @@ struct PlanBuilder {
     }
 };
 
-int get_plan(ftc_text* h, int B, std::shared_ptr<TextPlan>* out) {
+// n = 0: the plan of a whole call with B rows; 1 <= n < B: the decoder pass over n compact slots in the layout of B
+int get_plan(ftc_text* h, int B, std::shared_ptr<TextPlan>* out, int n = 0) {
     if (!h) return ftc_set_error(FTC_ERR_INVALID, "ftc_text: null handle");
     if (B < 1 || B > FTC_TEXT_MAX_BATCH) return ftc_set_error(FTC_ERR_INVALID, "ftc_text: B must be in 1.." + std::to_string(FTC_TEXT_MAX_BATCH) + " (split the batch)");
+    if (n < 0 || n >= B) n = 0;
     std::lock_guard<std::mutex> lk(h->mu);
-    auto it = h->plans.find(B);
+    const std::pair<int, int> key(B, n);
+    auto it = h->plans.find(key);
     if (it == h->plans.end()) {
         std::shared_ptr<TextPlan> p(new (std::nothrow) TextPlan());
         if (!p) return ftc_set_error(FTC_ERR_NOMEM, "ftc_text: out of host memory");
         p->B = B;
-        PlanBuilder pb{h, p.get(), B, {}};
+        p->n = n ? n : B;
+        PlanBuilder pb{h, p.get(), B, p->n, {}};
         const int rc = pb.build();
         if (rc != FTC_OK) return rc;
-        it = h->plans.emplace(B, std::move(p)).first;
+        it = h->plans.emplace(key, std::move(p)).first;
     }
     *out = it->second;
     return FTC_OK;
@@ -533,6 +565,60 @@ int ftc_text_predict(ftc_text* h, const void* weights_dev, const float* enc_inpu
     return rc;
 }
 
+int ftc_text_compact_abi_version(void) { return FTC_TEXT_COMPACT_ABI_VERSION; }
+
+int ftc_text_predict_compact(ftc_text* h, const void* weights_dev, const float* enc_input, int B, int L, int64_t* ids, float* probs, int64_t* trace_tokens,
+                             int64_t* trace_codes, float* trace_probs, int flags, int* passes_run, int* rows_run, void* workspace, void* stream) {
+    if (!weights_dev || !enc_input || !ids || !probs || !workspace) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_predict_compact: null pointer argument");
+    if (flags & FTC_TEXT_NO_READBACK)
+        return ftc_set_error(FTC_ERR_INVALID, "ftc_text_predict_compact: FTC_TEXT_NO_READBACK is refused: the number of rows of the next pass is read back after "
+                                              "every pass (ftc_text_predict is the loop that runs without a host read)");
+    std::shared_ptr<TextPlan> p, cp;
+    int rc = get_plan(h, B, &p);
+    if (rc != FTC_OK) return rc;
+    char* ws = static_cast<char*>(workspace);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Layout& L_ = p->L;
+    int64_t* tokens = reinterpret_cast<int64_t*>(ws + L_.tokens);
+    int64_t* codes = reinterpret_cast<int64_t*>(ws + L_.codes);
+    float* scores = reinterpret_cast<float*>(ws + L_.scores);
+    int32_t* done = reinterpret_cast<int32_t*>(ws + L_.flags);
+    int32_t* active = done + FTC_TEXT_MAX_BATCH;
+    int32_t* map = active + FTC_TEXT_PASSES;
+    float* lg[3];
+    for (int i = 0; i < 3; ++i) lg[i] = reinterpret_cast<float*>(ws + L_.logit[i]);
+    const Ctx c{ws, static_cast<const char*>(weights_dev), s, tokens, {lg[0], lg[1], lg[2]}};
+    if (rows_run) std::memset(rows_run, 0, sizeof(int) * FTC_TEXT_PASSES);
+    rc = encode(h, *p, c, enc_input, B, L, nullptr);
+    if (rc != FTC_OK) return rc;
+    rc = PlanBuilder::hip(ftc_text_fill_tokens_launch(tokens, (int64_t)B * S, FTC_TEXT_MASK_TOKEN, s), "token fill");
+    if (rc == FTC_OK) rc = PlanBuilder::hip(hipMemsetAsync(done, 0, (FTC_TEXT_MAX_BATCH + FTC_TEXT_PASSES) * 4, s), "flag reset");
+    int pass = 0, n = B;                     // n rows run in this pass; n < B: slot j is row map[j]
+    for (; rc == FTC_OK && pass < FTC_TEXT_PASSES; ++pass) {
+        rc = run(n == B ? p->dec : cp->dec, c);
+        if (rc == FTC_OK)
+            rc = PlanBuilder::hip(ftc_text_select_launch(lg[0], lg[1], lg[2], MOD[0], MOD[1], MOD[2], (int64_t)n * S, codes, scores, nullptr, nullptr, s), "selection");
+        if (rc == FTC_OK)
+            rc = PlanBuilder::hip(ftc_text_row_update_rows_launch(tokens, codes, scores, B, n, pass, n == B ? nullptr : map, done, active, ids, probs, trace_tokens,
+                                                                  trace_codes, trace_probs, s), "row update");
+        if (rc == FTC_OK && rows_run) rows_run[pass] = n;
+        if (rc == FTC_OK && pass + 1 < FTC_TEXT_PASSES) {
+            int32_t still = 0;
+            rc = PlanBuilder::hip(ftc_text_row_map_launch(done, B, map, s), "row map");
+            if (rc == FTC_OK) rc = PlanBuilder::hip(hipMemcpyAsync(&still, active + pass, 4, hipMemcpyDeviceToHost, s), "active-row read");
+            if (rc == FTC_OK) rc = PlanBuilder::hip(hipStreamSynchronize(s), "active-row read");
+            if (rc == FTC_OK && still == 0) { ++pass; break; }
+            if (rc == FTC_OK && (still < 0 || still > n)) rc = ftc_set_error(FTC_ERR_HIP, "ftc_text_predict_compact: the active-row count grew between passes");
+            if (rc == FTC_OK && still != n) {
+                n = still;
+                rc = get_plan(h, B, &cp, n);
+            }
+        }
+    }
+    if (passes_run) *passes_run = pass;
+    return rc;
+}
+
 static bool ld_ok(int64_t ld, int heads) { return ld >= 64 * (int64_t)heads && ld % 4 == 0; }
 
 int ftc_text_attention(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad, float* out,
@@ -543,6 +629,19 @@ int ftc_text_attention(const float* q, int64_t ldq, const float* k, int64_t ldk,
     if (!ld_ok(ldq, heads) || !ld_ok(ldk, heads) || !ld_ok(ldv, heads) || !ld_ok(ldo, heads) || ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16)
         return ftc_set_error(FTC_ERR_INVALID, "ftc_text_attention: row pitches must be multiples of 4 floats and at least 64 * heads, q / k / v 16-byte aligned");
     return PlanBuilder::hip(ftc_text_attention_launch(q, ldq, k, ldk, v, ldv, key_pad, out, ldo, B, heads, Sq, Sk, static_cast<hipStream_t>(stream)), "attention");
+}
+
+int ftc_text_attention_rows(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad,
+                            const int32_t* kv_row, int Bkv, float* out, int64_t ldo, int B, int heads, int Sq, int Sk, void* stream) {
+    if (!q || !k || !v || !out) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_attention_rows: null pointer argument");
+    if (B < 1 || B > 65535 || Bkv < 1 || Bkv > 65535 || heads < 1 || heads > 1024 || Sq < 1 || Sq > S || Sk < 1 || Sk > S)
+        return ftc_set_error(FTC_ERR_INVALID, "ftc_text_attention_rows: B, Bkv, heads >= 1 and 1 <= Sq, Sk <= " + std::to_string(S));
+    if (!kv_row && Bkv != B) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_attention_rows: a NULL kv_row is the identity and needs Bkv == B");
+    if (!ld_ok(ldq, heads) || !ld_ok(ldk, heads) || !ld_ok(ldv, heads) || !ld_ok(ldo, heads) || ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || (uintptr_t)kv_row % 4)
+        return ftc_set_error(FTC_ERR_INVALID, "ftc_text_attention_rows: row pitches must be multiples of 4 floats and at least 64 * heads, q / k / v 16-byte aligned");
+    // the entries of kv_row are device data: the kernel checks each against Bkv before it forms an address
+    return PlanBuilder::hip(ftc_text_attention_rows_launch(q, ldq, k, ldk, v, ldv, key_pad, kv_row, Bkv, out, ldo, B, heads, Sq, Sk, static_cast<hipStream_t>(stream)),
+                            "attention");
 }
 
 int ftc_text_rownorm(const float* a, const float* b, const float* pos_in, const float* gamma, const float* beta, const float* pos_out,

@@ -12,7 +12,11 @@
 //      index); the position's result is that choice's code point and KEY (all 27 invalid -> choice 0 with score 0).
 //
 // maskpredict_row_update: one workgroup per row, the reference's two stop tests and the re-mask rule kept PER ROW (the reference couples
-// the rows of a batch through torch.all / torch.any; here a row is the reference run on that row alone).
+// the rows of a batch through torch.all / torch.any; here a row is the reference run on that row alone).  With a row map (the compact
+// passes of include/ftc_text_compact.h) workgroup j reads the codes / scores of slot j and owns row map[j] of everything else.
+//
+// maskpredict_row_map: one wave64, B <= 64.  Lane l holds row l; one ballot over `done`, and a row still running takes the slot
+// "population count of the lower lanes": the running rows in ascending order, with no atomics and no ordering between workgroups.
 #include "ftc_common.h"
 #include "ftc_host.h"
 #include "crt_wave.h"
@@ -114,20 +118,21 @@ __global__ __launch_bounds__(64 * MS_WAVES) void maskpredict_select_kernel(const
 }
 
 __global__ __launch_bounds__(256) void maskpredict_row_update_kernel(int64_t* __restrict__ tokens, const int64_t* __restrict__ codes,
-                                                                     const float* __restrict__ scores, int B, int pass, int32_t* __restrict__ done,
+                                                                     const float* __restrict__ scores, int B, int pass,
+                                                                     const int32_t* __restrict__ map, int32_t* __restrict__ done,
                                                                      int32_t* __restrict__ active, int64_t* __restrict__ ids, float* __restrict__ probs,
                                                                      int64_t* __restrict__ tr_tokens, int64_t* __restrict__ tr_codes,
                                                                      float* __restrict__ tr_probs) {
     __shared__ int fails, remasks;
-    const int b = blockIdx.x;
-    if (done[b]) return;                     // block-uniform
+    const int b = map ? map[blockIdx.x] : blockIdx.x;
+    if (b < 0 || b >= B || done[b]) return;  // block-uniform
     if (threadIdx.x == 0) { fails = 0; remasks = 0; }
     __syncthreads();
-    const int64_t base = (int64_t)b * MS_LEN, tbase = ((int64_t)pass * B + b) * MS_LEN;
+    const int64_t base = (int64_t)b * MS_LEN, tbase = ((int64_t)pass * B + b) * MS_LEN, slot = (int64_t)blockIdx.x * MS_LEN;
     int f = 0, m = 0;
     for (int i = threadIdx.x; i < MS_LEN; i += 256) {
-        const int64_t t = tokens[base + i], c = codes[base + i];
-        const float p = scores[base + i];
+        const int64_t t = tokens[base + i], c = codes[slot + i];
+        const float p = scores[slot + i];
         if (tr_tokens) tr_tokens[tbase + i] = t;
         if (tr_codes) tr_codes[tbase + i] = c;
         if (tr_probs) tr_probs[tbase + i] = p;
@@ -139,8 +144,8 @@ __global__ __launch_bounds__(256) void maskpredict_row_update_kernel(int64_t* __
     __syncthreads();
     const bool stop = fails == 0 || pass == MS_PASSES - 1 || remasks == 0;
     for (int i = threadIdx.x; i < MS_LEN; i += 256) {
-        const int64_t c = codes[base + i];
-        const float p = scores[base + i];
+        const int64_t c = codes[slot + i];
+        const float p = scores[slot + i];
         if (stop) { ids[base + i] = c; probs[base + i] = p; }
         else tokens[base + i] = (p < 0.9f || c > MS_LIMIT) ? MS_MASK : c;
     }
@@ -148,6 +153,13 @@ __global__ __launch_bounds__(256) void maskpredict_row_update_kernel(int64_t* __
         if (stop) done[b] = 1;
         else atomicAdd(&active[pass], 1);
     }
+}
+
+__global__ __launch_bounds__(64) void maskpredict_row_map_kernel(const int32_t* __restrict__ done, int B, int32_t* __restrict__ map) {
+    const int lane = threadIdx.x;
+    const bool live = lane < B && done[lane] == 0;
+    const uint64_t running = __ballot(live);
+    if (live) map[__popcll(running & ((uint64_t(1) << lane) - 1))] = lane;
 }
 
 __global__ __launch_bounds__(256) void text_fill_tokens_kernel(int64_t* __restrict__ tokens, int64_t n, int64_t value) {
@@ -171,11 +183,24 @@ hipError_t ftc_text_select_launch(const float* l0, const float* l1, const float*
     return hipGetLastError();
 }
 
+// n workgroups: slot j is row map[j] of B (map == NULL: n == B, slot j is row j)
+hipError_t ftc_text_row_update_rows_launch(int64_t* tokens, const int64_t* codes, const float* scores, int B, int n, int pass, const int32_t* map,
+                                           int32_t* done, int32_t* active, int64_t* ids, float* probs, int64_t* tr_tokens, int64_t* tr_codes,
+                                           float* tr_probs, hipStream_t stream) {
+    if (B <= 0 || n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(maskpredict_row_update_kernel, dim3(map ? n : B), dim3(256), 0, stream, tokens, codes, scores, B, pass, map, done, active, ids, probs,
+                       tr_tokens, tr_codes, tr_probs);
+    return hipGetLastError();
+}
+
 hipError_t ftc_text_row_update_launch(int64_t* tokens, const int64_t* codes, const float* scores, int B, int pass, int32_t* done, int32_t* active,
                                       int64_t* ids, float* probs, int64_t* tr_tokens, int64_t* tr_codes, float* tr_probs, hipStream_t stream) {
-    if (B <= 0) return hipSuccess;
-    hipLaunchKernelGGL(maskpredict_row_update_kernel, dim3(B), dim3(256), 0, stream, tokens, codes, scores, B, pass, done, active, ids, probs, tr_tokens,
-                       tr_codes, tr_probs);
+    return ftc_text_row_update_rows_launch(tokens, codes, scores, B, B, pass, nullptr, done, active, ids, probs, tr_tokens, tr_codes, tr_probs, stream);
+}
+
+hipError_t ftc_text_row_map_launch(const int32_t* done, int B, int32_t* map, hipStream_t stream) {
+    if (B <= 0 || B > 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(maskpredict_row_map_kernel, dim3(1), dim3(64), 0, stream, done, B, map);
     return hipGetLastError();
 }
 

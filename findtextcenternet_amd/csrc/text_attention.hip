@@ -12,6 +12,11 @@
 //      segments).  The two key halves are added through LDS in a fixed order and stored as 128-byte segments.
 // Every row's result depends on that row's operands only, in an order that does not depend on B: rows of a batch are bitwise the rows
 // computed alone.  No allocation, no synchronisation.
+//
+// kv_row (optional, int32 [B]): query batch b reads the keys, values and key padding of batch kv_row[b] of Bkv -- the compact passes of
+// the mask-predict loop (include/ftc_text_compact.h), whose queries sit in n contiguous slots while K / V stay where the B-row layout
+// put them.  The index is uniform per workgroup: one extra load and three base pointers, nothing changes in the MFMA loops.  An entry
+// outside [0, Bkv) never becomes an address: the workgroup writes quiet NaNs to its part of the slot and leaves.
 #include "ftc_common.h"
 #include "ftc_host.h"
 
@@ -24,16 +29,26 @@ constexpr int TA_SPLIT = 208;                   // P.V: keys [0, 208) and [208, 
 
 __global__ __launch_bounds__(256) void text_attention_kernel(const float* __restrict__ q, int64_t ldq, const float* __restrict__ k, int64_t ldk,
                                                              const float* __restrict__ v, int64_t ldv, const uint8_t* __restrict__ pad,
-                                                             float* __restrict__ out, int64_t ldo, int Sq, int Sk) {
+                                                             const int32_t* __restrict__ kv_row, int Bkv, float* __restrict__ out, int64_t ldo,
+                                                             int Sq, int Sk) {
     __shared__ float S[32 * TA_SP];
     __shared__ float R[2 * 32 * 33];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int q0 = blockIdx.x * 32, head = blockIdx.y, b = blockIdx.z;
+    int kvb = b;
+    if (kv_row) {
+        kvb = kv_row[b];
+        if (kvb < 0 || kvb >= Bkv) {            // workgroup-uniform: no barrier has been reached
+            for (int i = threadIdx.x; i < 32 * 64; i += 256)
+                if (q0 + (i >> 6) < Sq) out[((int64_t)b * Sq + q0 + (i >> 6)) * ldo + head * 64 + (i & 63)] = __builtin_nanf("");
+            return;
+        }
+    }
     const float* qb = q + ((int64_t)b * Sq) * ldq + head * 64;
-    const float* kb = k + ((int64_t)b * Sk) * ldk + head * 64;
-    const float* vb = v + ((int64_t)b * Sk) * ldv + head * 64;
-    const uint8_t* pb = pad ? pad + (int64_t)b * Sk : nullptr;
+    const float* kb = k + ((int64_t)kvb * Sk) * ldk + head * 64;
+    const float* vb = v + ((int64_t)kvb * Sk) * ldv + head * 64;
+    const uint8_t* pb = pad ? pad + (int64_t)kvb * Sk : nullptr;
 
     // ---- 1. scores
     f32x4 qf[8];
@@ -131,8 +146,14 @@ __global__ __launch_bounds__(256) void text_attention_kernel(const float* __rest
 
 }  // namespace
 
+hipError_t ftc_text_attention_rows_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad,
+                                          const int32_t* kv_row, int Bkv, float* out, int64_t ldo, int B, int heads, int Sq, int Sk, hipStream_t stream) {
+    hipLaunchKernelGGL(text_attention_kernel, dim3((Sq + 31) / 32, heads, B), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, key_pad, kv_row, Bkv, out, ldo,
+                       Sq, Sk);
+    return hipGetLastError();
+}
+
 hipError_t ftc_text_attention_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad,
                                      float* out, int64_t ldo, int B, int heads, int Sq, int Sk, hipStream_t stream) {
-    hipLaunchKernelGGL(text_attention_kernel, dim3((Sq + 31) / 32, heads, B), dim3(256), 0, stream, q, ldq, k, ldk, v, ldv, key_pad, out, ldo, Sq, Sk);
-    return hipGetLastError();
+    return ftc_text_attention_rows_launch(q, ldq, k, ldk, v, ldv, key_pad, nullptr, B, out, ldo, B, heads, Sq, Sk, stream);
 }

@@ -7,6 +7,8 @@
 //                  LayerNorm after a residual add, with the block tails' second skip connection (x + _x came out of the GEMM's
 //                  epilogue, `b` adds the block input), and the NEXT attention's query / key input y + pos_emb_q as a second output
 //                  (the reference adds the position table before the q / k projections and not to the value input, :101-123);
+//                  tok_row (optional, with tokens): the tokens of slot row / S are those of batch row tok_row[row / S] of tok_rows
+//                  (the compact passes of include/ftc_text_compact.h; an entry outside [0, tok_rows) reads token 0);
 //   text_swiglu    w1(x) * silu(wg(x)) on the output of the merged [w1 | wg] GEMM;
 //   text_pad_input glyph vectors [B][L][106] -> [B][400][128] zero-padded rows for the embed GEMM, and the key-padding mask
 //                  (a vector that is all zeros, :239-240; rows L .. 399 are padding too).
@@ -25,7 +27,8 @@ __global__ __launch_bounds__(64 * TO_WAVES) void text_rownorm_kernel(const float
                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                    const float* __restrict__ pos_out, const int64_t* __restrict__ tokens,
                                                                    const float* __restrict__ e0, const float* __restrict__ e1, const float* __restrict__ e2,
-                                                                   float* __restrict__ out, float* __restrict__ out_pos, int64_t rows, int S, int E) {
+                                                                   const int32_t* __restrict__ tok_row, int tok_rows, float* __restrict__ out,
+                                                                   float* __restrict__ out_pos, int64_t rows, int S, int E) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * TO_WAVES + (threadIdx.x >> 6);
     if (row >= rows) return;                 // whole waves leave: no barrier follows
@@ -35,7 +38,12 @@ __global__ __launch_bounds__(64 * TO_WAVES) void text_rownorm_kernel(const float
     float x[J];
     int64_t t0 = 0, t1 = 0, t2 = 0;
     if (tokens) {
-        int64_t t = tokens[row];
+        int64_t at = row;
+        if (tok_row) {
+            const int src = tok_row[row / S];
+            at = src >= 0 && src < tok_rows ? (int64_t)src * S + row % S : -1;
+        }
+        int64_t t = at >= 0 ? tokens[at] : 0;
         if (t < 0) t = 0;
         t0 = (t % 1091) * E; t1 = (t % 1093) * E; t2 = (t % 1097) * E;
     }
@@ -110,16 +118,22 @@ __global__ __launch_bounds__(64 * TO_WAVES) void text_pad_input_kernel(const flo
 
 }  // namespace
 
-hipError_t ftc_text_rownorm_launch(const float* a, const float* b, const float* pos_in, const float* gamma, const float* beta, const float* pos_out,
-                                   const int64_t* tokens, const float* e0, const float* e1, const float* e2, float* out, float* out_pos,
-                                   int64_t rows, int S, int E, hipStream_t stream) {
+hipError_t ftc_text_rownorm_rows_launch(const float* a, const float* b, const float* pos_in, const float* gamma, const float* beta, const float* pos_out,
+                                        const int64_t* tokens, const float* e0, const float* e1, const float* e2, const int32_t* tok_row, int tok_rows,
+                                        float* out, float* out_pos, int64_t rows, int S, int E, hipStream_t stream) {
     if (rows <= 0) return hipSuccess;
     const dim3 grid((unsigned)((rows + TO_WAVES - 1) / TO_WAVES)), block(64 * TO_WAVES);
     if (E <= 768)
-        hipLaunchKernelGGL(text_rownorm_kernel<12>, grid, block, 0, stream, a, b, pos_in, gamma, beta, pos_out, tokens, e0, e1, e2, out, out_pos, rows, S, E);
+        hipLaunchKernelGGL(text_rownorm_kernel<12>, grid, block, 0, stream, a, b, pos_in, gamma, beta, pos_out, tokens, e0, e1, e2, tok_row, tok_rows, out, out_pos, rows, S, E);
     else
-        hipLaunchKernelGGL(text_rownorm_kernel<TO_MAXJ>, grid, block, 0, stream, a, b, pos_in, gamma, beta, pos_out, tokens, e0, e1, e2, out, out_pos, rows, S, E);
+        hipLaunchKernelGGL(text_rownorm_kernel<TO_MAXJ>, grid, block, 0, stream, a, b, pos_in, gamma, beta, pos_out, tokens, e0, e1, e2, tok_row, tok_rows, out, out_pos, rows, S, E);
     return hipGetLastError();
+}
+
+hipError_t ftc_text_rownorm_launch(const float* a, const float* b, const float* pos_in, const float* gamma, const float* beta, const float* pos_out,
+                                   const int64_t* tokens, const float* e0, const float* e1, const float* e2, float* out, float* out_pos,
+                                   int64_t rows, int S, int E, hipStream_t stream) {
+    return ftc_text_rownorm_rows_launch(a, b, pos_in, gamma, beta, pos_out, tokens, e0, e1, e2, nullptr, 0, out, out_pos, rows, S, E, stream);
 }
 
 hipError_t ftc_text_swiglu_launch(const float* in, float* out, int64_t rows, int H, hipStream_t stream) {

@@ -8,8 +8,14 @@ as if chunk k+1 depended on chunk k's text; it does not: where a chunk starts an
 and how many leading characters of its text are dropped again are functions of the six flag columns only, and those come from the
 ``linedetect`` reply.  So a page is PLANNED before anything is recognized (``plan_chunks``: two small integer tables), its chunks are
 assembled on the device from the feature rows the page merge left there (``ftc_ocr_assemble``, include/ftc_ocr.h) and decoded in batched
-``ftc_text_predict`` calls (``recognize_layout``); since every row of a batch is bitwise the row decoded alone, the page's text is exactly
+recognizer calls (``recognize_layouts``); since every row of a batch is bitwise the row decoded alone, the page's text is exactly
 what the chunk-by-chunk loop gives.  ``build_result`` turns the predictions into the reference's result dict.
+
+Many pages.  The same two facts let chunks of DIFFERENT pages share a batch: ``pool_plans`` merges the pages' tables (glyph indices and
+chunk starts shifted by each page's base), ``recognize_layouts`` runs the pool in groups of up to 64 rows through ``ftc_ocr_assemble``
+and the compact mask-predict loop (include/ftc_text_compact.h: a row that has stopped leaves the batch, so a full batch does not
+run until its slowest row stops), and ``ocr_pages`` / ``call_OCR_files`` detect page k + 1 while ``linedetect`` children of the
+pages before it run on the CPU (``run_pages``).  No page's result changes by one bit.
 
 Table formats.  ``ChunkPlan.rows`` int32 [R, 2]: glyph index (or -1 for the separator row the reference inserts on a line or block
 change) and flag bits -- bit 0 vertical, 1 ruby base, 2 ruby text, 3 space, 4 emphasis, 5 newline, the reference's six extra columns in
@@ -21,8 +27,9 @@ import json
 import os
 import re
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -32,7 +39,9 @@ from .page import PageDetector, linedetect_parse, linedetect_request
 from .schema import decoder_EOT, decoder_PAD, decoder_SOT, feature_dim, max_decoderlen, max_encoderlen
 from .transformer import HipTextBackend, TransformerPredictor, _stream, _target_device, predict_device
 
-__all__ = ["ChunkPlan", "plan_chunks", "build_result", "recognize_layout", "OCR_hip_Processer", "decode_ruby"]
+__all__ = ["ChunkPlan", "PlanPool", "plan_chunks", "pool_plans", "build_result", "recognize_layout", "recognize_layouts", "run_pages",
+           "OCR_hip_Processer", "decode_ruby"]
+MAX_LINEDETECT_WORKERS = 4                   # the children are CPU programs next to the process that feeds the GPU
 
 VERTICAL, RUBY_BASE, RUBY_TEXT, SPACE, EMPHASIS, NEWLINE = (1 << k for k in range(6))
 MAX_CHUNK_ROWS = max_encoderlen - 3          # the reference keeps one position spare besides the two tokens
@@ -183,6 +192,51 @@ def plan_chunks(reply, n_glyphs: int) -> ChunkPlan:
     return ChunkPlan(rows, fidx, chunks, int(n_glyphs))
 
 
+@dataclass
+class PlanPool:
+    """The row tables of several pages as one: what ``ftc_ocr_assemble`` reads when the pages' feature rows are concatenated."""
+    rows: np.ndarray                                      # int32 [sum R_k, 2]: glyph index + the page's glyph base (or -1), flag bits
+    chunks: np.ndarray                                    # int32 [sum n_chunks_k, 2]: first row + the page's row base, row count
+    counts: List[int]                                     # chunks per page, in page order
+    n_glyphs: int
+
+    def groups(self, size: int = L.TEXT_MAX_BATCH) -> List[Tuple[int, int]]:
+        """The recognizer batches: [lo, hi) ranges of at most ``size`` chunks, in pool order."""
+        n = self.chunks.shape[0]
+        return [(lo, min(n, lo + size)) for lo in range(0, n, size)]
+
+    def split(self, preds: np.ndarray) -> List[np.ndarray]:
+        """[sum n_chunks_k, 400] -> one array per page."""
+        edges = np.cumsum([0] + self.counts)
+        return [preds[edges[k]:edges[k + 1]] for k in range(len(self.counts))]
+
+
+def pool_plans(plans: Sequence[ChunkPlan]) -> PlanPool:
+    """Host only.  Page k's glyph indices are shifted by the glyphs of the pages before it, its chunk starts by their rows; separators
+    stay -1.  A table that names a glyph its page does not have is refused with the page's index."""
+    rows, chunks, counts = [], [], []
+    glyph_base = row_base = 0
+    for k, plan in enumerate(plans):
+        r = np.asarray(plan.rows, dtype=np.int32).reshape(-1, 2)
+        if r.shape[0] and (int(r[:, 0].min()) < -1 or int(r[:, 0].max()) >= plan.n_glyphs):
+            bad = int(r[(r[:, 0] < -1) | (r[:, 0] >= plan.n_glyphs), 0][0])
+            raise ValueError(f"page {k}: the row table names glyph {bad}, but the page has only {plan.n_glyphs}")
+        table = plan.chunk_table
+        if table.shape[0] and (int(table[:, 0].min()) < 0 or int((table[:, 0] + table[:, 1]).max()) > r.shape[0]):
+            raise ValueError(f"page {k}: a chunk lies outside the page's {r.shape[0]} rows")
+        r = r.copy()
+        r[r[:, 0] >= 0, 0] += glyph_base
+        table = table.copy()
+        table[:, 0] += row_base
+        rows.append(r)
+        chunks.append(table)
+        counts.append(int(table.shape[0]))
+        glyph_base += int(plan.n_glyphs)
+        row_base += int(r.shape[0])
+    cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros((0, 2), np.int32)      # noqa: E731
+    return PlanPool(cat(rows), cat(chunks), counts, glyph_base)
+
+
 # ------------------------------------------------------------------------------------------------
 # predictions -> the result dict (process_ocr_base.py:236-250, 285-465)
 # ------------------------------------------------------------------------------------------------
@@ -317,48 +371,105 @@ def assemble_device(glyphfeatures: torch.Tensor, rows_d: torch.Tensor, chunks_d:
     return enc[:B * Lmax * (feature_dim + L.OCR_FLAGS)].view(B, Lmax, feature_dim + L.OCR_FLAGS)
 
 
-def recognize_layout(model2, glyphfeatures, plan: ChunkPlan) -> np.ndarray:
-    """Every chunk of a planned page through the recognizer: int64 [n_chunks, 400], row k bitwise ``call_transformer`` on chunk k's input.
-    ``glyphfeatures``: the CUDA fp32 tensor [M, 100] of ``detect_page(..., return_tensors=True)`` (a NumPy array is uploaded once)."""
-    if isinstance(model2, HipTextBackend):
-        model2 = model2.model2
-    if not isinstance(model2, TransformerPredictor):
-        raise TypeError("recognize_layout expects a findtextcenternet_amd TransformerPredictor")
-    n = len(plan.chunks)
-    result = np.empty((n, L.TEXT_LEN), dtype=np.int64)
-    if n == 0:
-        return result
-    dev = _target_device(model2)
+def _page_features(glyphfeatures, plan: ChunkPlan, dev) -> torch.Tensor:
     if not torch.is_tensor(glyphfeatures):
         glyphfeatures = torch.from_numpy(np.ascontiguousarray(glyphfeatures, dtype=np.float32))
     gf = glyphfeatures.to(device=dev, dtype=torch.float32).contiguous()
     if gf.dim() != 2 or gf.shape[1] != feature_dim or gf.shape[0] != plan.n_glyphs:
         raise ValueError(f"glyphfeatures must be [{plan.n_glyphs}, {feature_dim}], got {tuple(gf.shape)}")
-    table = plan.chunk_table
+    return gf
+
+
+def recognize_layouts(model2, pages, stats: Optional[dict] = None, _compact: bool = True) -> List[np.ndarray]:
+    """Every chunk of several planned pages through the recognizer, the chunks of all pages pooled in page order and decoded in
+    batches of up to 64 rows: ``pages`` = a list of (glyphfeatures, ChunkPlan), the result a list of int64 [n_chunks_k, 400] whose rows
+    are bitwise ``call_transformer`` on that chunk's input.  Pages without chunks are legal anywhere.  ``glyphfeatures``: the CUDA fp32
+    tensor [M, 100] of ``detect_page(..., return_tensors=True)`` (a NumPy array is uploaded once).  ``stats``: a dict that receives
+    ``chunks``, ``batches``, ``passes`` (per batch) and ``row_passes`` (rows computed, summed over passes and batches)."""
+    if isinstance(model2, HipTextBackend):
+        model2 = model2.model2
+    if not isinstance(model2, TransformerPredictor):
+        raise TypeError("recognize_layouts expects a findtextcenternet_amd TransformerPredictor")
+    pages = list(pages)
+    pool = pool_plans([plan for _, plan in pages])
+    n = int(pool.chunks.shape[0])
+    result = np.empty((n, L.TEXT_LEN), dtype=np.int64)
+    if stats is not None:
+        stats.update(chunks=n, batches=0, passes=[], row_passes=0)
+    if n == 0:
+        return pool.split(result)
+    dev = _target_device(model2)
+    feats = [_page_features(gf, plan, dev) for gf, plan in pages]
+    gf = feats[0] if len(feats) == 1 else torch.cat(feats)
+    table = pool.chunks
     if int(table[:, 1].max()) + 2 > L.TEXT_LEN:
         raise ValueError("a chunk is longer than the recognizer's input")
-    rows_d = torch.from_numpy(plan.rows).to(dev)
+    rows_d = torch.from_numpy(pool.rows).to(dev)
     chunks_d = torch.from_numpy(table).to(dev)
     buf = model2.__dict__.get("_layout_buffers")
     if buf is None:
         buf = _LayoutBuffers()
         object.__setattr__(model2, "_layout_buffers", buf)
     eng = model2._engine
-    for lo in range(0, n, L.TEXT_MAX_BATCH):
-        hi = min(n, lo + L.TEXT_MAX_BATCH)
+    for lo, hi in pool.groups():
         B, Lmax = hi - lo, int(table[lo:hi, 1].max()) + 2
         buf.fit(dev, B, Lmax)
         x = assemble_device(gf, rows_d, chunks_d[lo:hi], Lmax, buf.enc)
         nb = B * L.TEXT_LEN * 12
-        predict_device(eng, x, out=buf.out[:nb])
+        out = predict_device(eng, x, out=buf.out[:nb], compact=_compact)
         buf.host[:nb].copy_(buf.out[:nb])
         result[lo:hi] = buf.host[:8 * B * L.TEXT_LEN].numpy().view(np.int64).reshape(B, L.TEXT_LEN)
-    return result
+        if stats is not None:
+            stats["batches"] += 1
+            stats["passes"].append(out[3])
+            stats["row_passes"] += sum(out[4]) if _compact else B * out[3]
+    return pool.split(result)
+
+
+def recognize_layout(model2, glyphfeatures, plan: ChunkPlan) -> np.ndarray:
+    """``recognize_layouts`` for one page: int64 [n_chunks, 400], row k bitwise ``call_transformer`` on chunk k's input."""
+    return recognize_layouts(model2, [(glyphfeatures, plan)])[0]
+
+
+def run_pages(pages: Sequence, detect: Callable, linedetect: Callable, recognize: Callable, window: int = 8, workers: int = MAX_LINEDETECT_WORKERS,
+              names: Optional[Sequence[str]] = None, deliver: Optional[Callable] = None) -> list:
+    """The page loop of ``ocr_pages`` over three stages, so that it runs without a GPU on stubs.  Per window of ``window`` pages:
+    ``detect(page) -> det`` page by page on the calling thread, each ``linedetect(det) -> reply`` handed to a pool of ``workers`` threads
+    as soon as its page is detected (so page k + 1 is detected while the line finder of page k runs), then, when the window's replies
+    are in, ``recognize([(det, reply), ...]) -> [result, ...]`` once.  Results come back in page order; ``deliver(k, result)`` is called
+    for the pages of a finished window in order.  A ``linedetect`` that raises fails the call with the same kind of error, extended by the
+    page's index (and name), after the other children of the window have been waited for; that window delivers nothing."""
+    if window < 1:
+        raise ValueError("window must be at least 1")
+    workers = max(1, min(int(workers), MAX_LINEDETECT_WORKERS))
+    pages = list(pages)
+    results = []
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        for lo in range(0, len(pages), window):
+            dets, futures = [], []
+            try:
+                for page in pages[lo:lo + window]:
+                    dets.append(detect(page))
+                    futures.append(pool.submit(linedetect, dets[-1]))
+            finally:
+                failures = [(lo + i, f.exception()) for i, f in enumerate(futures) if f.exception() is not None]      # waits for every child
+            if failures:
+                k, err = failures[0]
+                where = f"page {k}" + (f", {names[k]}" if names is not None else "")
+                raise type(err)(f"{err} ({where})") if isinstance(err, (RuntimeError, ValueError)) else RuntimeError(f"{err!r} ({where})") from err
+            out = list(recognize([(d, f.result()) for d, f in zip(dets, futures)]))
+            if len(out) != len(dets):
+                raise RuntimeError(f"the recognize stage returned {len(out)} results for {len(dets)} pages")
+            for i, r in enumerate(out):
+                if deliver is not None:
+                    deliver(lo + i, r)
+            results += out
+    return results
 
 
 class OCR_hip_Processer:
     """The fourth backend next to the reference's ``OCR_{torch,onnx,coreml}_Processer``, complete in itself: ``call_OCR(target_file)`` reads
-    an image and writes ``target_file + '.json'``; ``ocr_page(im_u8)`` is the same without file I/O.  ``linedetect`` is the reference's line
+    an image and writes ``target_file + '.json'``; ``ocr_page(im_u8)`` is the same without file I/O; ``ocr_pages`` / ``call_OCR_files`` do many pages at once.  ``linedetect`` is the reference's line
     finder (``textline_detect``), a separate program the user builds from the reference; it runs as a child process on the CPU."""
 
     def __init__(self, model_size: str = "xl", precision: Optional[str] = None, text_precision: Optional[str] = None,
@@ -421,12 +532,45 @@ class OCR_hip_Processer:
         preds = recognize_layout(self.transformer, glyph_d, plan)
         return build_result(plan, preds, locations, resize)
 
-    def call_OCR(self, target_file: str, resize: float = 1.0) -> dict:
+    def ocr_pages(self, pages, resize: float = 1.0, window: int = 8, linedetect_workers: int = MAX_LINEDETECT_WORKERS, names=None, deliver=None) -> list:
+        """``[ocr_page(p, resize) for p in pages]`` with the work of a window of pages shared: page k + 1 is detected while the
+        ``linedetect`` children of the pages before it run (at most ``linedetect_workers`` <= 4 at a time), and the chunks of the
+        window's pages are recognized in shared batches (``recognize_layouts``).  Every result equals ``ocr_page``'s.  ``pages`` may be a
+        list of images or of callables that return one (``call_OCR_files`` opens its files that way, one window at a time)."""
+        def detect(page):
+            im = page() if callable(page) else page
+            return self.page_detector.detect_page(im, return_tensors=True)
+
+        def recognize(items):
+            plans = [plan_chunks(reply, det[0].shape[0]) for det, reply in items]
+            preds = recognize_layouts(self.transformer, [(det[1], plan) for (det, _), plan in zip(items, plans)])
+            return [build_result(plan, pr, det[0], resize) for (det, _), plan, pr in zip(items, plans, preds)]
+
+        return run_pages(pages, detect, lambda det: self.run_linedetect(det[0], det[2], det[3]), recognize, window=window, workers=linedetect_workers,
+                         names=names, deliver=deliver)
+
+    @staticmethod
+    def _open_page(target_file: str, resize: float) -> np.ndarray:
         from PIL import Image
         im0 = Image.open(target_file).convert("RGB")
         if resize != 1.0:
             im0 = im0.resize((int(im0.width * resize), int(im0.height * resize)), resample=Image.Resampling.BILINEAR)
-        result = self.ocr_page(np.array(im0), resize)                     # (a writable copy: the page is uploaded with torch.from_numpy)
+        return np.array(im0)                                              # (a writable copy: the page is uploaded with torch.from_numpy)
+
+    @staticmethod
+    def _write_json(target_file: str, result: dict) -> None:
         with open(target_file + ".json", "w", encoding="utf-8") as f:
             json.dump(result, f, indent=2, ensure_ascii=False)
+
+    def call_OCR(self, target_file: str, resize: float = 1.0) -> dict:
+        result = self.ocr_page(self._open_page(target_file, resize), resize)
+        self._write_json(target_file, result)
         return result
+
+    def call_OCR_files(self, files, resize: float = 1.0, window: int = 8, linedetect_workers: int = MAX_LINEDETECT_WORKERS) -> list:
+        """``[call_OCR(f, resize) for f in files]`` through ``ocr_pages``: every ``<file>.json`` is byte for byte ``call_OCR``'s.  The files of
+        a window are written when that window is finished; if a page fails, the files of the windows before it stay and its own window
+        writes none."""
+        files = [os.fspath(f) for f in files]
+        pages = [lambda f=f: self._open_page(f, resize) for f in files]
+        return self.ocr_pages(pages, resize, window, linedetect_workers, names=files, deliver=lambda k, result: self._write_json(files[k], result))

@@ -236,9 +236,12 @@ def teacher_forced(eng: _TextEngine, x: torch.Tensor, dec_input: torch.Tensor, p
     return enc_out, (outs if passes else outs[0])
 
 
-def predict_device(eng: _TextEngine, x: torch.Tensor, out: Optional[torch.Tensor] = None, trace: bool = False, readback: bool = True):
+def predict_device(eng: _TextEngine, x: torch.Tensor, out: Optional[torch.Tensor] = None, trace: bool = False, readback: bool = True,
+                   compact: bool = False):
     """``ftc_text_predict`` on x [B, L, 106] (CUDA fp32 contiguous): (ids int64 [B,400], probs fp32 [B,400], traces or None, passes).
-    ids and probs are views of ONE byte buffer (``out``, B * 400 * 12 bytes: ids first), so one copy brings both to the host."""
+    ids and probs are views of ONE byte buffer (``out``, B * 400 * 12 bytes: ids first), so one copy brings both to the host.
+    ``compact``: ``ftc_text_predict_compact`` (include/ftc_text_compact.h) instead -- the rows that have stopped are taken out of every
+    later pass, the values are bitwise the same -- and a fifth result, ``rows_run``: the rows computed in each of the 8 passes."""
     lib = L.load()
     dev = x.device
     B, Lx = int(x.shape[0]), int(x.shape[1])
@@ -255,8 +258,14 @@ def predict_device(eng: _TextEngine, x: torch.Tensor, out: Optional[torch.Tensor
                   torch.zeros((L.TEXT_PASSES, B, L.TEXT_LEN), dtype=torch.float32, device=dev))
         tp = [t.data_ptr() for t in tr] if tr else [None, None, None]
         passes = C.c_int(0)
+        flags = 0 if readback else L.TEXT_NO_READBACK
+        if compact:
+            rows_run = (C.c_int * L.TEXT_PASSES)()
+            L.check(lib.ftc_text_predict_compact(eng.handle, eng.wdev.data_ptr(), x.data_ptr(), B, Lx, ids.data_ptr(), probs.data_ptr(), tp[0], tp[1], tp[2],
+                                                 flags, C.byref(passes), rows_run, ws.data_ptr(), _stream(dev)), "ftc_text_predict_compact")
+            return ids, probs, tr, int(passes.value), list(rows_run)
         L.check(lib.ftc_text_predict(eng.handle, eng.wdev.data_ptr(), x.data_ptr(), B, Lx, ids.data_ptr(), probs.data_ptr(), tp[0], tp[1], tp[2],
-                                     0 if readback else L.TEXT_NO_READBACK, C.byref(passes), ws.data_ptr(), _stream(dev)), "ftc_text_predict")
+                                     flags, C.byref(passes), ws.data_ptr(), _stream(dev)), "ftc_text_predict")
     return ids, probs, tr, int(passes.value)
 
 
