@@ -8,6 +8,7 @@ from .glyphs import crt_codepoint, decode_glyphs   # noqa: F401
 from .transformer import HipTextBackend, ModelDimensions, Transformer, TransformerPredictor, recognize_chunks   # noqa: F401
 from .weights import deterministic_state_dict, load_tf_efficientnetv2_npz, recognizer_state_dict  # noqa: F401
 from .page import PageDetector, linedetect_parse, linedetect_request, page_merge_gpu   # noqa: F401
+from .prelabel import prelabel_file, prelabel_page, sample_page   # noqa: F401
 from .ocr import OCR_hip_Processer, build_result, plan_chunks, pool_plans, recognize_layout, recognize_layouts, run_pages   # noqa: F401
 from .optim import AdamWScheduleFree   # noqa: F401
 from .train_step import TrainStep   # noqa: F401
@@ -16,5 +17,5 @@ from . import synth   # noqa: F401
 
 __all__ = ["TextDetectorModel", "CenterNetDetection", "CenterNetDetector", "SimpleDecoder", "CodeDecoder", "decode_glyphs", "crt_codepoint", "HipDetectorBackend", "ModelDimensions", "Transformer", "TransformerPredictor", "HipTextBackend", "recognize_chunks", "recognizer_state_dict",
            "TileGeom", "Decoded", "decode_peaks", "tiles_to_device", "exact_logit_cut", "tile_keep_rect", "deterministic_state_dict", "load_tf_efficientnetv2_npz", "PageDetector", "page_merge_gpu", "linedetect_request",
-           "linedetect_parse", "OCR_hip_Processer", "plan_chunks", "build_result", "recognize_layout", "recognize_layouts", "pool_plans", "run_pages", "AdamWScheduleFree", "TrainStep", "DetectorLanes",
+           "linedetect_parse", "prelabel_page", "prelabel_file", "sample_page", "OCR_hip_Processer", "plan_chunks", "build_result", "recognize_layout", "recognize_layouts", "pool_plans", "run_pages", "AdamWScheduleFree", "TrainStep", "DetectorLanes",
            "width", "height", "scale", "feature_dim", "modulo_list"]

@@ -51,6 +51,10 @@ FTC_OCR_ABI_VERSION = 1
 OCR_FEATURE_DIM, OCR_FLAGS = 100, 6
 OCR_EXPORTS = ["ftc_ocr_abi_version", "ftc_ocr_assemble"]
 
+# include/ftc_prep.h (data preparation: the fill selection of the pre-labeller / feature sampler, glyph features at given centres)
+FTC_PREP_ABI_VERSION = 1
+PREP_EXPORTS = ["ftc_prep_abi_version", "ftc_page_ink", "ftc_page_fill_scratch_bytes", "ftc_page_fill", "ftc_features_at"]
+
 
 class FtcLibraryError(RuntimeError):
     pass
@@ -199,6 +203,14 @@ def load():
     lib.ftc_text_attention_rows.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i32, vp, i64, i32, i32, i32, i32, vp]
     lib.ftc_ocr_abi_version.restype = i32
     lib.ftc_ocr_assemble.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp, vp]
+    lib.ftc_prep_abi_version.restype = i32
+    lib.ftc_page_ink.argtypes = [vp, i32, vp, i32, i32, C.c_float, vp, vp, vp]
+    lib.ftc_page_fill_scratch_bytes.argtypes = [i32, i32, i32]
+    lib.ftc_page_fill_scratch_bytes.restype = i64
+    lib.ftc_page_fill.argtypes = [vp, vp, i32, vp, vp, vp, C.c_float, C.c_double, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]
+    lib.ftc_features_at.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp]
+    if lib.ftc_prep_abi_version() != FTC_PREP_ABI_VERSION:
+        raise FtcLibraryError(f"prep ABI mismatch: library {lib.ftc_prep_abi_version()} vs binding {FTC_PREP_ABI_VERSION}")
     if lib.ftc_ocr_abi_version() != FTC_OCR_ABI_VERSION:
         raise FtcLibraryError(f"OCR ABI mismatch: library {lib.ftc_ocr_abi_version()} vs binding {FTC_OCR_ABI_VERSION}")
     if lib.ftc_text_compact_abi_version() != FTC_TEXT_COMPACT_ABI_VERSION:

@@ -29,6 +29,15 @@ bool ftc_fmbconv_legal(const ftc_op& o);
 // conv_igemm.hip: NULL if the convolution op (incl. its tuned kernel choice ftc_op.aux0) is supported, else the reason
 const char* conv_validate(const ftc_op& op);
 
+// page_merge.hip: the header block in the scratch of the rank-ordered page selections (ftc_page_merge; ftc_page_fill in page_fill.hip) and the two
+// of its kernels both use -- the exclusive prefix sum of the neighbour counts (more edges than `cap`: use_seq = 1) and the kept ranks -> keep_idx
+struct PmHdr { int n_keep, ticket, use_seq, big_lock, total_edges, stall_r, stall_j, stall_n; };      // stall_*: the first wait that ran into the spin limit
+hipError_t launch_pm_scan(int* cnt, int* cursor, int N, long cap, PmHdr* hdr, hipStream_t s);
+hipError_t launch_pm_compact(const int* status, const int* order, int N, int* keep_idx, PmHdr* hdr, hipStream_t s);
+// page_merge.hip: the tail of both selections -- separator filter (seps > sep_th; NaN: none) and 3x3 code maxima behind a keep list
+hipError_t launch_page_finish(const float* loc, const int* keep_idx, const int* n_keep, const float* seps, const float* codes, int mh, int mw, int scale,
+                              double sep_th, float* out_loc, int* out_idx, int* out_n, hipStream_t s);
+
 // glyph_select.hip: the per-glyph code-point selection kernel behind ftc_glyph_select / ftc_glyph_decode (arguments validated by the caller)
 hipError_t ftc_glyph_select_launch(const float* l0, const float* l1, const float* l2, int64_t ld0, int64_t ld1, int64_t ld2, int n,
                                    float* s0, float* s1, float* s2, int64_t* ids, float* probs, hipStream_t stream);

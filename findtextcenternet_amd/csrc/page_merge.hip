@@ -9,6 +9,7 @@
 // bitmap (LDS bit image + popcount).  All arithmetic is IEEE float64 with contraction off, integer histogram sums are
 // exact, so the results are bit-identical to the reference's.
 #include "ftc_common.h"
+#include "ftc_host.h"
 
 #pragma clang fp contract(off)
 
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(GT) void greedy_kernel(const float* __restrict__ lo
 // Every comparison is the greedy kernel's own float64 expression, so the result is bit-identical (tests/test_gpu_page.py).  If the
 // neighbour lists do not fit the scratch the caller gave, a device flag routes the page through the sequential kernel instead.
 // ------------------------------------------------------------------------------------------------------------------
-struct PmHdr { int n_keep, ticket, use_seq, big_lock, total_edges, stall_r, stall_j, stall_n; };      // stall_*: the first wait that ran into PM_SPIN_LIMIT
+// (struct PmHdr: ftc_host.h)
 constexpr int PM_T = 256;                  // candidates per tile of the all-pairs pass
 constexpr int PM_SPIN_LIMIT = 1 << 19;      // polls (~130 cycles apart) a wave waits for ONE neighbour before it hands the page to the sequential kernel
 constexpr int PM_WAVE_WORDS = 2048;        // LDS coverage image per wave: 65536 cells (larger boxes: one shared global image behind a lock)
@@ -631,7 +632,7 @@ __global__ __launch_bounds__(1024) void pm_median_kernel(const double* __restric
 __global__ __launch_bounds__(256) void finish_kernel(const float* __restrict__ loc, const int* __restrict__ keep_idx, const int* __restrict__ n_keep,
                                                      const float* __restrict__ seps, const float* __restrict__ codes, int mh, int mw, int scale,
                                                      float* __restrict__ out_loc, int* __restrict__ out_idx, int* __restrict__ out_n, const PmVar var,
-                                                     float* __restrict__ out_cmax) {
+                                                     float* __restrict__ out_cmax, const double sep_th /*0.5 here; the fill selection (page_fill.hip) passes its own, NaN = no filter*/) {
     // a single workgroup keeps the output order with a prefix count
     __shared__ int s_base;
     __shared__ int s_scan[256];
@@ -648,7 +649,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const float* __restrict__ l
             i = keep_idx[k];
             const double cx = pm_col(loc, i, 1, var), cy = pm_col(loc, i, 2, var);
             const long x = (long)(cx / scale), y = (long)(cy / scale);
-            ok = !(x >= 0 && x < mw && y >= 0 && y < mh && seps[y * mw + x] > 0.5f);
+            ok = !(x >= 0 && x < mw && y >= 0 && y < mh && (double)seps[y * mw + x] > sep_th);
         }
         s_scan[t] = ok ? 1 : 0;
         __syncthreads();
@@ -722,7 +723,25 @@ hipError_t launch_greedy(const float* loc, const int* order, int N, const double
     hipLaunchKernelGGL(pm_compact_kernel, dim3(1), dim3(1024), 0, s, status, order, N, keep_idx, hdr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, loc, keep_idx, (const int*)&hdr->n_keep, seps, codes, mh, mw, scale, out_loc, out_idx, out_n, var, out_cmax);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, loc, keep_idx, (const int*)&hdr->n_keep, seps, codes, mh, mw, scale, out_loc, out_idx, out_n, var, out_cmax, 0.5);
+    return hipGetLastError();
+}
+
+hipError_t launch_pm_scan(int* cnt, int* cursor, int N, long cap, PmHdr* hdr, hipStream_t s) {
+    hipLaunchKernelGGL(pm_scan_kernel, dim3(1), dim3(1024), 0, s, cnt, cursor, N, cap, hdr);
+    return hipGetLastError();
+}
+
+hipError_t launch_pm_compact(const int* status, const int* order, int N, int* keep_idx, PmHdr* hdr, hipStream_t s) {
+    hipLaunchKernelGGL(pm_compact_kernel, dim3(1), dim3(1024), 0, s, status, order, N, keep_idx, hdr);
+    return hipGetLastError();
+}
+
+// the separator filter and the code maxima alone, behind another selection's keep_idx / n_keep (page_fill.hip)
+hipError_t launch_page_finish(const float* loc, const int* keep_idx, const int* n_keep, const float* seps, const float* codes, int mh, int mw, int scale,
+                              double sep_th, float* out_loc, int* out_idx, int* out_n, hipStream_t s) {
+    const PmVar var{0, 0x7fffffff, 1.0};
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, s, loc, keep_idx, n_keep, seps, codes, mh, mw, scale, out_loc, out_idx, out_n, var, (float*)nullptr, sep_th);
     return hipGetLastError();
 }
 

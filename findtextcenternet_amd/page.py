@@ -55,14 +55,20 @@ def page_merge_gpu(boxes: torch.Tensor, feats: torch.Tensor, page, canv: torch.T
     ``variant="demo"``: the selection of the demo script's ``eval()`` (``/root/reference/test_image1_torch.py:152-240``: no contrast filter --
     ``page`` may be a ``(page_h, page_w)`` tuple --, its ``fill_map`` offsets) with rows ``[seed_start, N)`` = the UNSCALED boxes of a coarse
     first pass, multiplied by ``seed_scale`` in float64 inside the kernels (``:313-332``); returns (locations float64 [M,9] numpy -- eval()'s own
-    result rows: seed rows scaled, ``max(code maximum, code)`` in float64 --, glyphfeatures [M,C] device tensor)."""
+    result rows: seed rows scaled, ``max(code maximum, code)`` in float64 --, glyphfeatures [M,C] device tensor).
+
+    ``variant="sampler"`` / ``"prelabel"``: the fill selection of the reference's feature sampler (``make_traindata/process_torch.py:141-244``)
+    and annotation pre-labeller (``fine_image/process_image1_torch.py:183-298``), defined in ``include/ftc_prep.h``: ownership map, ink
+    rule, threshold = median contrast / 10; the pre-labeller also drops centres on separators above 0.1.  Returns (locations, glyphfeatures
+    [M,C] device tensor) with locations = a float32 device tensor for the sampler and eval()'s float64 numpy rows for the pre-labeller."""
     lib = L.load()
     dev = boxes.device
     boxes = boxes.contiguous()
     N = boxes.shape[0]
     demo = variant == "demo"
-    if variant not in ("production", "demo"):
-        raise ValueError("variant must be 'production' or 'demo'")
+    fill = variant in ("sampler", "prelabel")
+    if variant not in ("production", "demo") and not fill:
+        raise ValueError("variant must be 'production', 'demo', 'sampler' or 'prelabel'")
     ph, pw = (page if demo and isinstance(page, tuple) else page.shape[:2])
     mh, mw = canv.shape[1:]
     with torch.cuda.device(dev):
@@ -83,6 +89,22 @@ def page_merge_gpu(boxes: torch.Tensor, feats: torch.Tensor, page, canv: torch.T
         out_loc = torch.empty((N, 9), dtype=torch.float32, device=dev)
         out_idx = torch.empty((N,), dtype=torch.int32, device=dev)
         out_n = torch.zeros((1,), dtype=torch.int32, device=dev)
+        if fill:
+            # the threshold the kernels use is th * 0.5 (median / 10), formed on the device: bit-identical, halving commutes with rounding
+            ink = torch.empty((N,), dtype=torch.int64, device=dev)
+            L.check(lib.ftc_page_ink(boxes.data_ptr(), N, page.data_ptr(), ph, pw, C.c_float(cut_off), th.data_ptr(), ink.data_ptr(), stream), "ftc_page_ink")
+            nbytes = int(lib.ftc_page_fill_scratch_bytes(N, ph, pw))
+            scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            codes = canv[3:7].contiguous()
+            L.check(lib.ftc_page_fill(boxes.data_ptr(), order.data_ptr(), N, hist[1].data_ptr(), th.data_ptr(), ink.data_ptr(), C.c_float(cut_off),
+                                      C.c_double(0.1 if variant == "prelabel" else float("nan")), canv[2].data_ptr(), codes.data_ptr(), mh, mw, scale, ph, pw,
+                                      out_loc.data_ptr(), out_idx.data_ptr(), out_n.data_ptr(), scratch.data_ptr(), nbytes, stream), "ftc_page_fill")
+            n = int(out_n.item())
+            if n < 0:
+                raise RuntimeError("ftc_page_fill: the order table names a row outside the candidate block")
+            gf = feats.index_select(0, out_idx[:n].long())
+            # the pre-labeller's rows are float64 arrays of float32 values (max of two float32 values widened = the float64 max)
+            return (out_loc[:n].cpu().numpy().astype(np.float64) if variant == "prelabel" else out_loc[:n]), gf
         nbytes = int(lib.ftc_page_merge_scratch_bytes(N, ph, pw))
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         codes = canv[3:7].contiguous()
@@ -124,9 +146,13 @@ class PageDetector:
         """variant="demo": the tiling, border margins and page-level selection of the demo script instead of the production class --
         ``/root/reference/test_image1_torch.py``: step = 3/4 of a tile (``:298-299``), 1/8 margins (``:103-108``), ``eval()``'s selection
         (``:152-240``; float64 result rows); ``twopass`` (its command-line switch, ``:313-332``): a page of more than 2 steps is first run
-        shrunk onto ONE tile and the boxes found there join the candidates of the full-resolution pass, scaled back."""
-        if variant not in ("production", "demo"):
-            raise ValueError("variant must be 'production' or 'demo'")
+        shrunk onto ONE tile and the boxes found there join the candidates of the full-resolution pass, scaled back.
+
+        variant="sampler" / "prelabel": the page loops of the reference's data-preparation programs -- ``make_traindata/process_torch.py:69-244``
+        (float32 result rows) and ``fine_image/process_image1_torch.py:113-298`` (float64 rows, separator filter): the demo script's tiling and
+        margins with the fill selection (``include/ftc_prep.h``).  Both call it with ``cut_off=0.4``."""
+        if variant not in ("production", "demo", "sampler", "prelabel"):
+            raise ValueError("variant must be 'production', 'demo', 'sampler' or 'prelabel'")
         if twopass and variant != "demo":
             raise ValueError("twopass is the demo script's mode: variant='demo'")
         self.variant, self.twopass = variant, bool(twopass)
@@ -146,8 +172,8 @@ class PageDetector:
         self._lane_streams, self._lane_ws = None, {}
         self._row_hint = None                                  # rows per tile the last page needed (multi-GPU gather of large blocks)
         self.stepx, self.stepy = int(width * step_ratio), int(height * step_ratio)      # process_ocr_base.py:43-45
-        if variant == "demo":
-            self.stepx, self.stepy = width * 3 // 4, height * 3 // 4                     # test_image1_torch.py:298-299
+        if variant != "production":
+            self.stepx, self.stepy = width * 3 // 4, height * 3 // 4                     # test_image1_torch.py:298-299, process_torch.py:24-25
 
     # -- reference signature -----------------------------------------------------------------
     def run_detector(self, ds: Sequence[dict], org_img: np.ndarray):
@@ -205,13 +231,72 @@ class PageDetector:
             raise RuntimeError("coarse-pass rows are not fp32 values")              # (cannot happen: no seed rows in the coarse pass)
         return torch.from_numpy(loc0.astype(np.float32)).to(self.device), torch.from_numpy(gf0).to(self.device), float(s_)
 
+    def features_at(self, im_u8: np.ndarray, centers: np.ndarray, return_tensors: bool = False):
+        """Glyph features at GIVEN centres -- ``eval()`` of ``fine_image/process_image4_torch.py:70-100``: centers [K,2] (x, y) in page pixels ->
+        float16 [K,100].  Always the 3/4-step tiling with 1/8 margins, white padding as ``detect_page``; the tile batches alternate over the lanes.
+        A centre gets the feature row of the LAST tile (in tile order) whose margin window holds it strictly inside; unclaimed centres stay 0.
+        The tile is found on the GPU from the page's whole tile table (``ftc_features_at``), so the result does not depend on ``batch`` or ``lanes``."""
+        lib = L.load()
+        h0, w0 = im_u8.shape[:2]
+        stepx, stepy = width * 3 // 4, height * 3 // 4
+        ph, pw = padded_page_size(h0, w0, stepx, stepy)
+        origins = tile_origins(ph, pw, stepx, stepy)
+        cen = np.ascontiguousarray(np.asarray(centers, dtype=np.float32).reshape(-1, 2))
+        K = cen.shape[0]
+        n_batches = (len(origins) + self.batch - 1) // self.batch
+        n_lanes = min(self.lanes, max(1, n_batches))
+        with torch.cuda.device(self.device), torch.no_grad():
+            main = torch.cuda.current_stream(self.device)
+            page_dev = torch.from_numpy(np.ascontiguousarray(im_u8[:, :, :3])).to(self.device)
+            o_all = torch.tensor(origins, dtype=torch.int32, device=self.device).reshape(-1, 2)
+            cen_d = torch.from_numpy(cen).to(self.device)
+            out = torch.zeros((K, feature_dim), dtype=torch.float16, device=self.device)
+            tl_all = tiles_to_device([TileGeom(ox, oy, pw, ph, tile_keep_rect(ox, oy, pw, ph, None)) for (oy, ox) in origins], self.device,
+                                     height // scale, width // scale)
+            streams = self._lane_setup(n_lanes, main)
+            if n_lanes > 1:
+                for s_ in streams:
+                    s_.wait_stream(main)
+            for k, lo in enumerate(range(0, len(origins), self.batch)):
+                hi = min(len(origins), lo + self.batch)
+                lane = k % n_lanes
+                with torch.cuda.stream(streams[lane]):
+                    stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+                    x = torch.empty((hi - lo, height, width, 3), dtype=torch.float32, device=self.device)
+                    L.check(lib.ftc_tile_gather(page_dev.data_ptr(), h0, w0, o_all[lo:hi].data_ptr(), hi - lo, height, width, x.data_ptr(), stream), "ftc_tile_gather")
+                    _, feat = self.detector.forward_nhwc(x.permute(0, 3, 1, 2), workspace=self._lane_ws[lane] if n_lanes > 1 else None)
+                    feat = feat.contiguous()
+                    if feat.dtype != torch.float32 or feat.shape[3] != feature_dim:
+                        raise RuntimeError("features_at: the detector's feature block is not float32 [B,h,w,%d]" % feature_dim)
+                    L.check(lib.ftc_features_at(cen_d.data_ptr(), K, tl_all.data_ptr(), len(origins), lo, hi - lo, feat.data_ptr(), feat.shape[1], feat.shape[2],
+                                                feature_dim, scale, out.data_ptr(), stream), "ftc_features_at")
+            if n_lanes > 1:
+                for s_ in streams:
+                    main.wait_stream(s_)
+            return out if return_tensors else out.cpu().numpy()
+
     # -- shared ------------------------------------------------------------------------------------
+    def _lane_setup(self, n_lanes: int, main):
+        """The streams the batches of a page alternate over (``[main]`` for one lane), with an activation arena per lane."""
+        if n_lanes <= 1:
+            return [main]
+        if self._lane_streams is None or len(self._lane_streams) < n_lanes:
+            self._lane_streams = [torch.cuda.Stream(device=self.device) for _ in range(n_lanes)]
+        eng = self.detector.detector._engine
+        eng.ensure_model(self.device)
+        need = eng.model.workspace_bytes(self.batch, height, width)
+        for i in range(n_lanes):
+            if i not in self._lane_ws or self._lane_ws[i].numel() < need:
+                self._lane_ws[i] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._lane_streams[:n_lanes]
+
     def _run(self, get_tiles, origins, page_hw, page_f32, seeds=None, cut_off=None, world1=False, return_tensors=False):
         """get_tiles(lo, hi) -> [n,768,768,3] fp32 0..1 on the GPU; page_hw = (padded) page size; page_f32() -> the padded fp32 page on the GPU.
         seeds (demo variant) = (locations0 fp32 [K,9] unscaled, glyphfeatures0 [K,C], scale) of a coarse pass; world1: no sharding (the coarse pass)."""
         lib = L.load()
         cut = self.cut_off if cut_off is None else cut_off
         demo = self.variant == "demo"
+        eighth = self.variant != "production"                 # the demo script's 1/8 margins (the data-preparation programs have the same)
         page_h, page_w = page_hw
         mh, mw = page_h // scale, page_w // scale
         canv = torch.zeros((7, mh, mw), dtype=torch.float32, device=self.device)
@@ -224,21 +309,10 @@ class PageDetector:
         n_lanes = min(self.lanes, max(1, n_batches))
         with torch.cuda.device(self.device), torch.no_grad():
             main = torch.cuda.current_stream(self.device)
-            if n_lanes > 1:
-                if self._lane_streams is None or len(self._lane_streams) < n_lanes:
-                    self._lane_streams = [torch.cuda.Stream(device=self.device) for _ in range(n_lanes)]
-                streams = self._lane_streams[:n_lanes]
-                eng = self.detector.detector._engine
-                eng.ensure_model(self.device)
-                need = eng.model.workspace_bytes(self.batch, height, width)
-                for i in range(n_lanes):
-                    if i not in self._lane_ws or self._lane_ws[i].numel() < need:
-                        self._lane_ws[i] = torch.empty(need, dtype=torch.uint8, device=self.device)
-            else:
-                streams = [main]
+            streams = self._lane_setup(n_lanes, main)
             # every tile's geometry record in ONE upload, before any forward is enqueued: a host-to-device copy from pageable memory waits for
             # the stream it is issued on, and inside the loop that was the forward just enqueued (round 4: 2-4 ms of GPU idle per batch)
-            geoms = [TileGeom(ox, oy, page_w, page_h, tile_keep_rect(ox, oy, page_w, page_h, None if demo else self.step_ratio)) for (oy, ox) in origins[first:last]]
+            geoms = [TileGeom(ox, oy, page_w, page_h, tile_keep_rect(ox, oy, page_w, page_h, None if eighth else self.step_ratio)) for (oy, ox) in origins[first:last]]
             tl_all = tiles_to_device(geoms, self.device, height // scale, width // scale) if geoms else None
             if n_lanes > 1:
                 for s_ in streams:
@@ -285,7 +359,7 @@ class PageDetector:
                 loc_d, glyph_d = page_merge_gpu(boxes, fts, (page_h, page_w), canv, cut, variant="demo", seed_start=n_tile_rows,
                                                 seed_scale=seeds[2] if seeds is not None else 1.0)
             else:
-                loc_d, glyph_d = page_merge_gpu(boxes, fts, page_f32(), canv, cut)
+                loc_d, glyph_d = page_merge_gpu(boxes, fts, page_f32(), canv, cut, variant=self.variant)
             cmax = int(counts.max().item())
             if cmax > self.max_boxes:
                 raise RuntimeError(f"a tile produced {cmax} peaks > max_boxes={self.max_boxes}; raise max_boxes")
@@ -295,7 +369,7 @@ class PageDetector:
                 # pass of the two-pass mode, whose per-rank results are only equal if the GPUs agree bit for bit.
                 self._row_hint = min(self.max_boxes, (cmax + cmax // 4 + 64) // 64 * 64)
             canv_h = canv[1:3].cpu().numpy()
-            return (loc_d if demo else loc_d.cpu().numpy()), (glyph_d if return_tensors else glyph_d.cpu().numpy()), canv_h[0], canv_h[1]
+            return (loc_d if isinstance(loc_d, np.ndarray) else loc_d.cpu().numpy()), (glyph_d if return_tensors else glyph_d.cpu().numpy()), canv_h[0], canv_h[1]
 
 
 def linedetect_request(locations: np.ndarray, lines: np.ndarray, seps: np.ndarray) -> bytes:
