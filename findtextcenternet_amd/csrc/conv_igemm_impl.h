@@ -306,6 +306,9 @@ template <typename OutT> __host__ __device__ constexpr int epi_pitch(int tn) { r
 
 template <typename OutT> __device__ __forceinline__ bool epi_lds_ok(const ConvP& p) {
     constexpr int V = 16 / (int)sizeof(OutT);
+    // a 16-bit image would round the activated value BEFORE the residual is added and the sum once more (the direct, row and split-K
+    // epilogues round once): such ops -- none in the plans, whose residual trunk is fp32 -- take the other path
+    if (sizeof(OutT) == 2 && (p.flags & FTC_FLAG_RESIDUAL)) return false;
     return ((p.Cout | p.CoutT | p.cout_off) % V) == 0 && (p.Cout % 8) == 0;
 }
 

@@ -1166,6 +1166,7 @@ def test_fused_mbconv_block_in_one_launch(shape, dt):
     # of one of E terms -- the same budget as the MBHEAD test, which carries the same kind of intermediate
     lim = 2e-5 if x3 else 6e-3 if dt == L.BF16 else 1e-3
     assert err < lim and err_two < lim
+    assert torch.equal(out, two), (shape, dt, int((out != two).sum()), err_two)       # same rounding points and K order: the SAME bits as the two launches
     if x3:
         raw = ar.buf[o_out2:o_out2 + B * H * W * Cout * 4].cpu()
         assert float((_unsplit_f16x3(raw, (B, H, W, Cout)) - out).abs().max()) <= 3e-6 * float(out.abs().max())
