@@ -5,6 +5,7 @@
 // /root/reference/models/detector.py:12-28 (structure restated in SURVEY.md Appendix D), and the
 // input scaling of CenterNetDetection.forward (/root/reference/models/detector.py:218).
 #include "ftc_common.h"
+#include "ftc_host.h"
 
 namespace {
 
@@ -608,6 +609,9 @@ hipError_t launch_stem(const OpArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// stride 1: the strip kernel (16-bit: fast SiLU only; fp32: with or without activation).  0x100: the general kernel (A/B measurements, tests)
+bool ftc_dwconv_strip(const ftc_op& o) { return o.stride == 1 && !(o.flags & 0x100) && (ftc_is16(o.in_dtype) ? o.act != FTC_ACT_NONE : (o.Cin % 4 == 0)); }
+
 hipError_t launch_dwconv(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
     const int TH = o.stride == 1 ? 8 : 4, TW = 8;
@@ -616,8 +620,7 @@ hipError_t launch_dwconv(const OpArgs& a, hipStream_t s) {
     if (P != o.aux0) return hipErrorInvalidValue;
     // Consecutive tiles per workgroup: the grid runs in ceil(workgroups / resident slots) rounds of `tpw` tile
     // times each; take the tpw that minimises rounds * tpw (ties: the larger, it amortises the tap loads).
-    // stride 1: the strip kernel (16-bit: fast SiLU only; fp32: with or without activation).  0x100: the general kernel (A/B measurements, tests)
-    const bool strip = o.stride == 1 && !(o.flags & 0x100) && (ftc_is16(o.in_dtype) ? o.act != FTC_ACT_NONE : (o.Cin % 4 == 0));
+    const bool strip = ftc_dwconv_strip(o);
     const long slabs = (long)((o.Cin + 63) / 64) * o.B;
     const long slots = 256L * (strip ? (o.in_dtype == FTC_F32 ? 2 : 4) : o.in_dtype == FTC_F32 ? 3 : 2);     // workgroups resident on 256 CUs (LDS / VGPR-limited)
     int tpw = 1;

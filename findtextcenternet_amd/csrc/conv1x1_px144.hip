@@ -361,22 +361,26 @@ using namespace convimpl;
 template <typename T, int NCT>
 static hipError_t launch_px(ConvP& p, hipStream_t s) {
     using GM = PxGeom<NCT, is_x3<T>>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1x1_px144_kernel<T, NCT>), hipFuncAttributeMaxDynamicSharedMemorySize, GM::LDS);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(conv1x1_px144_kernel<T, NCT>), GM::LDS); e != hipSuccess) return e;
     p.nN = p.Cout / GM::TN;
     p.nblk = p.nN * (p.M / PX_TM);
     hipLaunchKernelGGL((conv1x1_px144_kernel<T, NCT>), dim3(p.nblk), dim3(GM::NT), GM::LDS, s, p);
     return hipGetLastError();
 }
 
-hipError_t launch_conv1x1_px144(const ConvP& p0, const ftc_op& o, hipStream_t s) {
+template <typename T>
+static hipError_t launch_px_tile(ConvP& p, int cfg, hipStream_t s) {
+    switch (cfg) {
+    case CFG_64x144: return launch_px<T, 4>(p, s);
+    case CFG_80x144: return launch_px<T, 5>(p, s);
+    case CFG_96x144: return launch_px<T, 6>(p, s);
+    case CFG_128x144: return launch_px<T, 8>(p, s);
+    default: return hipErrorInvalidValue;              // (conv_resolve hands this launcher only the x144 tiles)
+    }
+}
+
+hipError_t launch_conv1x1_px144(const ConvP& p0, const ConvChoice& c, hipStream_t s) {
     ConvP p = p0;
-    const int tn = kCfgTN[select_cfg(o)];
-    if (o.w_dtype == FTC_F32) return tn == 64 ? launch_px<x3f32, 4>(p, s) : tn == 80 ? launch_px<x3f32, 5>(p, s) : tn == 96 ? launch_px<x3f32, 6>(p, s) : launch_px<x3f32, 8>(p, s);
-    if (o.w_dtype == FTC_BF16) return tn == 64 ? launch_px<__bf16, 4>(p, s) : tn == 80 ? launch_px<__bf16, 5>(p, s) : tn == 96 ? launch_px<__bf16, 6>(p, s) : launch_px<__bf16, 8>(p, s);
-    return tn == 64 ? launch_px<_Float16, 4>(p, s) : tn == 80 ? launch_px<_Float16, 5>(p, s) : tn == 96 ? launch_px<_Float16, 6>(p, s) : launch_px<_Float16, 8>(p, s);
+    if (c.w_dtype == FTC_F32) return launch_px_tile<x3f32>(p, c.cfg, s);
+    return c.w_dtype == FTC_BF16 ? launch_px_tile<__bf16>(p, c.cfg, s) : launch_px_tile<_Float16>(p, c.cfg, s);
 }

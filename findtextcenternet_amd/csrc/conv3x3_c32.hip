@@ -142,33 +142,16 @@ static hipError_t launch_c32_t(ConvP p, hipStream_t s) {
     p.nN = 1;
     p.nblk = p.B * ((p.H + 15) / 16) * ((p.W + 15) / 16);
     if constexpr (is_x3<T>) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, C32Geom<T>::LDS);
-            if (e != hipSuccess) return e;
-            attr_set = true;
-        }
+        if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(kern), C32Geom<T>::LDS); e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(C32_NT), C32Geom<T>::LDS, s, p);
     return hipGetLastError();
 }
 
-// 16-bit operands of one type, fp32 output (+ optional 16-bit NHWC copy), 3x3 stride 1 "same", exactly 32 -> 32 whole-tensor channels, one group, no SE scale /
-// per-image weights / border bias / fused forms; fp32 residual
-bool conv3x3_c32_legal(const ftc_op& o) {
-    static const bool off = [] { const char* e = std::getenv("FTC_NO_C32"); return e && *e && *e != '0'; }();
-    if (off) return false;
-    const bool x3 = o.w_dtype == FTC_F32 && (o.flags & FTC_FLAG_SPLIT16);              // fp16x3: fp32 tensors, pre-split weights; out2 = the pre-split copy
-    static const bool off3 = [] { const char* e = std::getenv("FTC_NO_C32_X3"); return e && *e && *e != '0'; }();
-    if (x3 && off3) return false;
-    return (ftc_is16(o.w_dtype) || x3) && o.in_dtype == o.w_dtype && o.out_dtype == FTC_F32 && o.ksize == 3 && o.stride == 1 && o.Ho == o.H && o.Wo == o.W && o.Cin == 32 &&
-           o.Cin_total == 32 && o.cin_off == 0 && o.Cout == 32 && o.Cout_total == 32 && o.cout_off == 0 && o.groups <= 1 &&
-           (o.flags & ~(FTC_FLAG_RESIDUAL | (x3 ? FTC_FLAG_SPLIT16 : 0))) == 0 && (!(o.flags & FTC_FLAG_RESIDUAL) || o.res_dtype == FTC_F32);
-}
-
-hipError_t launch_conv3x3_c32(const ConvP& p, const ftc_op& o, hipStream_t s) {
-    if (o.w_dtype == FTC_F32) return launch_c32_t<x3f32>(p, s);
-    return o.w_dtype == FTC_F16 ? launch_c32_t<_Float16>(p, s) : launch_c32_t<__bf16>(p, s);
+// (which ops run here: conv3x3_c32_legal in conv_choice.h)
+hipError_t launch_conv3x3_c32(const ConvP& p, const ConvChoice& c, hipStream_t s) {
+    if (c.x3) return launch_c32_t<x3f32>(p, s);
+    return c.w_dtype == FTC_F16 ? launch_c32_t<_Float16>(p, s) : c.w_dtype == FTC_BF16 ? launch_c32_t<__bf16>(p, s) : hipErrorInvalidValue;
 }
 
 }  // namespace convimpl

@@ -2,6 +2,6 @@
 // split per combination so the ~20 tile/BK/buffering instantiations of each compile in parallel.
 #include "conv_igemm_impl.h"
 
-hipError_t launch_conv_f32(const convimpl::ConvP& p, const ftc_op& o, hipStream_t s) {
-    return convimpl::launch_types<float, float, float>(p, o, s);
+hipError_t launch_conv_f32(const convimpl::ConvP& p, const convimpl::ConvChoice& c, hipStream_t s) {
+    return convimpl::launch_types<float, float, float>(p, c, s);
 }

@@ -27,7 +27,9 @@
 #include <cstdio>
 #include <type_traits>
 
+#include "conv_choice.h"
 #include "ftc_common.h"
+#include "ftc_host.h"
 
 namespace convimpl {
 
@@ -50,7 +52,7 @@ struct ConvP {
     int nk;     // KS*KS*ncb
     int nN;     // channel tiles
     int nblk;   // total workgroups
-    int use_glds;   // direct-to-LDS kernel selected (uses_glds)
+    int use_glds;   // direct-to-LDS kernel selected (ConvChoice::ring > 1)
     int glds_nbuf;  // tuning: LDS ring depth of the DMA kernel (2 | 3)
     int split_k;    // tuning: K groups per workgroup of the register-staged kernel (1 | 2 | 4)
     int wset_bytes; // FTC_FLAG_W_PER_IMAGE: bytes between the weight sets of consecutive images (0 = one shared set)
@@ -1492,12 +1494,7 @@ hipError_t launch_halo(ConvP p, hipStream_t s) {
     constexpr size_t lds_bytes = halo_lds_bytes<WT, CPR, SN, TOPF, WMQ>();
     static_assert(!TOPF || (size_t)TY * 16 * TN * 2 + 16 * TN * 4 + 32 * TN * 2 <= lds_bytes, "image + bias rows + tap matrix must fit");
     auto kern = conv3x3_halo_kernel<WT, OutT, CPR, SN, TOPF, UPIN, WMQ>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes); e != hipSuccess) return e;
     p.ncb = p.Cin / (CPR * E);
     p.nk = 9 * p.ncb;
     p.nN = (p.Cout + TN - 1) / TN;
@@ -1830,16 +1827,9 @@ hipError_t launch_wl1(ConvP p, hipStream_t s) {
     constexpr int TY = 8 * WMH;
     constexpr size_t HBUF = (size_t)(TY + 2) * 18 * 128, LDS_MAX = 160 * 1024;
     auto kern = conv3x3_wl1_kernel<WT, OutT, TOPF, UPIN, WMH>;
-    static bool attr_set = false;
-    static int n_cu = 0;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-        if (e != hipSuccess) return e;
-        int dev = 0;
-        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        attr_set = true;
-    }
+    int n_cu = 0;
+    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(kern), (int)LDS_MAX); e != hipSuccess) return e;
+    if (hipError_t e = ftc_device_cus(&n_cu); e != hipSuccess) return e;
     p.ncb = p.Cin / 64;
     p.nk = 9 * p.ncb;
     p.nN = 1;
@@ -1874,13 +1864,7 @@ hipError_t launch_cfg2(ConvP p, hipStream_t s) {
     constexpr size_t lds_epi = KG == 1 ? (size_t)TM * epi_pitch<OutT>(TN) + (size_t)16 * TN * 4 : (size_t)KG * TM * epi_pitch<float>(TN);
     constexpr size_t lds_bytes = lds_stage > lds_epi ? lds_stage : lds_epi;
     auto kern = conv_igemm_kernel<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, SE, KG>;
-    static bool attr_set = false;     // per instantiation
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes); e != hipSuccess) return e;
     p.ncb = (p.Cin + BK - 1) / BK;
     p.nk = p.KS * p.KS * p.ncb;
     p.nN = (p.Cout + TN - 1) / TN;
@@ -1899,12 +1883,7 @@ hipError_t launch_glds(ConvP p, hipStream_t s) {
     constexpr size_t lds_epi = (size_t)TM * epi_pitch<OutT>(TN) + (size_t)16 * TN * 4;
     constexpr size_t lds_bytes = lds_stage > lds_epi ? lds_stage : lds_epi;
     auto kern = conv_igemm_glds_kernel<WT, OutT, BK, WN, WM, SN, SM, NBUF>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds_bytes); e != hipSuccess) return e;
     p.ncb = (p.Cin + BK - 1) / BK;
     p.nk = p.KS * p.KS * p.ncb;
     p.nN = (p.Cout + TN - 1) / TN;
@@ -1919,141 +1898,35 @@ hipError_t launch_cfg(const ConvP& p, hipStream_t s) {
     constexpr int E = 16 / (int)sizeof(WT);
     constexpr bool glds_ok = sizeof(WT) == sizeof(InT) && (BK / E == 8 || BK / E == 4) &&
                              (((WN * SN + WM * SM) * 32 * (BK / E)) % 256 == 0) && ((WN * SN * 32 * (BK / E)) % 64 == 0);
-    if constexpr (glds_ok) {
-        if (p.use_glds) {
+    if (p.use_glds) {
+        if constexpr (glds_ok) {
             if (p.flags & FTC_FLAG_SE_SCALE) return hipErrorInvalidValue;      // (glds_legal keeps such ops away: the DMA cannot rescale)
             if (p.glds_nbuf == 3) return launch_glds<WT, OutT, BK, WN, WM, SN, SM, 3>(p, s);
             return launch_glds<WT, OutT, BK, WN, WM, SN, SM, 2>(p, s);
         }
+        return hipErrorInvalidValue;                                           // (glds_legal: no DMA kernel of this tile / K step)
     }
     // intra-workgroup split-K (tuned per layer): long-K 1x1 convs on small tiles
-    if constexpr (sizeof(WT) == 2 && sizeof(InT) == 2 && WN * SN * WM * SM <= 8 && BK >= 64) {
-        if (p.split_k == 2) {
-            if (p.flags & FTC_FLAG_SE_SCALE) return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, true, 2>(p, s);
-            return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, false, 2>(p, s);
+    if (p.split_k != 1) {
+        if constexpr (sizeof(WT) == 2 && sizeof(InT) == 2 && WN * SN * WM * SM <= 8 && BK >= 64) {
+            if (p.split_k == 2) {
+                if (p.flags & FTC_FLAG_SE_SCALE) return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, true, 2>(p, s);
+                return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, false, 2>(p, s);
+            }
+            if (p.split_k == 4) {
+                if (p.flags & FTC_FLAG_SE_SCALE) return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, true, 4>(p, s);
+                return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, false, 4>(p, s);
+            }
         }
-        if (p.split_k == 4) {
-            if (p.flags & FTC_FLAG_SE_SCALE) return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, true, 4>(p, s);
-            return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, false, 4>(p, s);
-        }
+        return hipErrorInvalidValue;                                           // (splitk_legal: no split-K kernel of this tile / K step / type)
     }
     // the SE-scaled variant exists only where the network uses it: 1x1 project convs
     if (p.flags & FTC_FLAG_SE_SCALE) return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, true>(p, s);
     return launch_cfg2<WT, InT, OutT, BK, WN, WM, SN, SM, NBUF, false>(p, s);
 }
 
-// Tile configurations (output channels x output pixels per workgroup), in order of preference.
-// (tried in round 2 and removed: a 256x64 tile (4 waves side by side over N) for the wide MBConv expand GEMMs -- 0.6x the L2->LDS bytes
-//  per FLOP of the 64x64 tile -- never won in the tuner: gpurun_out/tuning_r2_1x1.log)
-// The x144 configs are a kernel of their own (conv1x1_px144.hip: 1x1, 16-bit operands, fp32 output), chosen only by hint.
-enum { CFG_192x128 = 0, CFG_128x128, CFG_96x128, CFG_64x128, CFG_128x64, CFG_32x256, CFG_64x64, CFG_64x144, CFG_80x144, CFG_128x144, CFG_96x144, CFG_COUNT };
-static const char* const kCfgName[] = {"192x128", "128x128", "96x128", "64x128", "128x64", "32x256", "64x64", "64x144", "80x144", "128x144", "96x144"};
-static const int kCfgTN[] = {192, 128, 96, 64, 128, 32, 64, 64, 80, 128, 96};
-static const int kCfgTM[] = {128, 128, 128, 128, 64, 256, 64, 144, 144, 144, 144};
-inline bool cfg_px144(int cfg) { return cfg >= CFG_64x144 && cfg <= CFG_96x144; }
-
-// ftc_op.aux0 carries the tuned kernel choice (0 = heuristics below): bits 0-3 tile config + 1,
-// bits 4-5 staging (1 = register-staged, 2 = direct-to-LDS 2-slot ring, 3 = 3-slot ring), bits 8-9 K step
-// (1 = 32, 2 = 64, 3 = 128).  The Python side fills it from a table measured on MI355X
-// (findtextcenternet_amd/tuning.py); the choices compute the same convolution -- bit-identical among the tile configs and stagings (same K
-// order), in another fp32 summation order with split-K and on the 144-pixel tiles.
-inline int hint_cfg(const ftc_op& o) { return (o.aux0 & 15) - 1; }
-inline bool hint_halo(const ftc_op& o) { return (o.aux0 & 64) != 0; }         // bit 6: LDS-halo 3x3 kernel
-inline bool hint_wl1(const ftc_op& o) { return (o.aux0 & 192) == 192; }       // bits 6+7: its weights-through-L1 successor (needs FTC_FLAG_W_FRAG weights)
-inline int hint_splitk(const ftc_op& o) { const int c = (o.aux0 >> 10) & 3; return c == 1 ? 2 : c == 2 ? 4 : 1; }   // bits 10-11
-inline int hint_stage(const ftc_op& o) { return (o.aux0 >> 4) & 3; }
-inline int hint_bk(const ftc_op& o) { const int b = (o.aux0 >> 8) & 3; return b == 1 ? 32 : b == 2 ? 64 : b == 3 ? 128 : 0; }
-
-inline int default_cfg(int n, int M) {
-    if (n <= 32) return CFG_32x256;
-    if (n <= 64) return CFG_64x128;
-    if (n <= 96) return CFG_96x128;
-    const long t192 = (long)((n + 191) / 192) * ((M + 127) / 128);
-    if (n % 192 == 0 && n % 128 != 0) return t192 >= 256 ? CFG_192x128 : CFG_64x64;
-    // 128-channel tiles; shrink the pixel tile when the grid would not fill the 256 CUs twice
-    const long tiles128 = (long)((n + 127) / 128) * ((M + 127) / 128);
-    return tiles128 < 512 ? CFG_128x64 : CFG_128x128;
-}
-inline int select_cfg(const ftc_op& o) {
-    const int h = hint_cfg(o);
-    if (h >= 0 && h < CFG_COUNT) return h;
-    const int d = default_cfg(o.Cout, o.B * o.Ho * o.Wo * (o.groups > 1 ? o.groups : 1));
-    // per-image weight sets: the pixel tile must divide the image
-    if ((o.flags & FTC_FLAG_W_PER_IMAGE) && (o.Ho * o.Wo) % kCfgTM[d]) return o.Cout > 64 ? CFG_128x64 : CFG_64x64;
-    return d;
-}
-inline bool px144_legal(const ftc_op& o, int cfg) {
-    // 16-bit operands, or the fp16x3 form with BOTH operands pre-split (fp32 tensors, FTC_FLAG_SPLIT16 | FTC_FLAG_PRESPLIT); K step 64
-    const bool x3 = o.w_dtype == FTC_F32 && (o.flags & FTC_FLAG_SPLIT16) && (o.flags & FTC_FLAG_PRESPLIT) && !(o.flags & FTC_FLAG_KBLOCK32);
-    const bool h16 = ftc_is16(o.w_dtype) && !(o.flags & FTC_FLAG_PRESPLIT);
-    const int ks = 64;
-    return o.ksize == 1 && o.stride == 1 && o.act == FTC_ACT_NONE && (x3 || h16) && o.in_dtype == o.w_dtype && o.out_dtype == FTC_F32 && o.Cin >= ks && o.Cin % ks == 0 &&
-           o.Cout % kCfgTN[cfg] == 0 && ((o.Cout_total | o.cout_off | o.Cin_total | o.cin_off) & 7) == 0 && (o.Ho * o.Wo) % 144 == 0 && o.groups <= 1 &&
-           !(o.flags & (FTC_FLAG_SE_SCALE | FTC_FLAG_BORDER_BIAS | FTC_FLAG_UPCAT_IN | FTC_FLAG_TOP_FUSE | FTC_FLAG_GROUP_OUT_SLICE));
-}
-inline bool wset_legal(const ftc_op& o) {
-    if (!(o.flags & FTC_FLAG_W_PER_IMAGE)) return true;
-    if (hint_halo(o)) return true;                                   // the halo kernel tiles each image separately
-    return (o.Ho * o.Wo) % kCfgTM[select_cfg(o)] == 0;
-}
-
-// K step: 64 for bf16 when the channel count allows (half the barriers per FLOP), else 32; 128 only by hint.
-inline int select_bk(const ftc_op& o) {
-    if (!ftc_is16(o.w_dtype)) return 32;
-    const int h = hint_bk(o);
-    if (h) return h;
-    return o.Cin % 64 == 0 ? 64 : 32;
-}
-inline bool glds_legal(const ftc_op& o) {
-    if (o.in_dtype != o.w_dtype) return false;
-    if (cfg_px144(select_cfg(o))) return false;
-    const int bk = select_bk(o);
-    if (bk == 128) return false;
-    const int cpr = bk / (ftc_is16(o.w_dtype) ? 8 : 4);
-    const int cfg = select_cfg(o);
-    if (o.flags & FTC_FLAG_SE_SCALE) return false;      // the SE scale is applied while staging through registers
-    // tiles must be a whole number of workgroup-level DMA passes
-    return ((kCfgTN[cfg] + kCfgTM[cfg]) * cpr) % 256 == 0 && (kCfgTN[cfg] * cpr) % 64 == 0;
-}
-inline bool uses_glds(const ftc_op& o) {
-    if (!glds_legal(o) || hint_splitk(o) > 1) return false;
-    const int st = hint_stage(o);
-    if (st) return st >= 2;
-    // Untuned default (tools/conv_bench.py, MI355X): the 2-slot DMA ring wins on the 192x128 and 64x128
-    // tiles (FPN: 819 vs 746 TF); on 128-channel tiles the register-staged kernel keeps 3-4 workgroups
-    // per CU with its single 36 KB buffer and is faster (stage2 3x3: 504 vs 439 TF).  fp32: DMA everywhere.
-    if (o.w_dtype == FTC_F32) return true;
-    const int cfg = select_cfg(o);
-    return cfg == CFG_192x128 || cfg == CFG_64x128;
-}
-inline int glds_ring(const ftc_op& o) { return hint_stage(o) == 3 ? 3 : 2; }
-// intra-workgroup split-K: register-staged kernel, bf16 activations, K step >= 64, tiles of <= 8 MFMA sub-tiles
-// (64x64, 64x128, 128x64), and a K loop that divides evenly
-inline bool splitk_legal(const ftc_op& o, int kg) {
-    if (kg == 1) return true;
-    if (!ftc_is16(o.w_dtype) || o.in_dtype != o.w_dtype || select_bk(o) < 64) return false;
-    const int cfg = select_cfg(o);
-    if (!(cfg == CFG_64x64 || cfg == CFG_64x128 || cfg == CFG_128x64)) return false;
-    const int bk = select_bk(o);
-    const long lds = (long)kg * (kCfgTN[cfg] + kCfgTM[cfg]) * (bk + 8) * 2;           // KG staging buffers (bf16, padded rows)
-    if (lds > 160 * 1024) return false;
-    const int nk = o.ksize * o.ksize * ((o.Cin + bk - 1) / bk);
-    return nk % kg == 0 && nk / kg >= 2;
-}
-// LDS-halo kernel: 3x3 stride 1, activations in the compute dtype, whole channel blocks, tile = 64/128/192 channels
-inline int halo_sn(const ftc_op& o) { const int c = select_cfg(o); return c == CFG_192x128 ? 3 : c == CFG_128x128 ? 2 : c == CFG_64x128 ? 1 : 0; }
-inline int halo_cpr(const ftc_op& o) {
-    if (o.w_dtype == FTC_F32) return o.Cin % 32 == 0 ? 8 : 0;
-    // 128-byte rows (K step 64) unless the channel count or the tuning hint (bk = 32) asks for 64-byte rows: those halve
-    // the LDS footprint, so two workgroups share a CU and one's epilogue overlaps the other's K loop
-    if (hint_bk(o) == 32 && hint_halo(o) && !(o.flags & (FTC_FLAG_TOP_FUSE | FTC_FLAG_UPCAT_IN))) return o.Cin % 32 == 0 ? 4 : 0;
-    return o.Cin % 64 == 0 ? 8 : (o.Cin % 32 == 0 ? 4 : 0);
-}
-inline bool halo_legal(const ftc_op& o) {
-    return o.ksize == 3 && o.stride == 1 && o.in_dtype == o.w_dtype && !(o.flags & FTC_FLAG_SE_SCALE) && halo_sn(o) > 0 && halo_cpr(o) > 0;
-}
-inline bool uses_halo(const ftc_op& o) { return hint_halo(o) && halo_legal(o); }
-
+// The launchers below take the ConvChoice of conv_resolve (conv_choice.h) and decide nothing from the ftc_op.  One that has no instantiation for the
+// choice it is handed returns hipErrorInvalidValue: conv_resolve refuses such ops at plan creation, so these returns are unreachable -- keep it that way.
 template <typename WT, typename InT, typename OutT, int BK>
 hipError_t launch_tiles(const ConvP& p, int cfg, hipStream_t s) {
     switch (cfg) {
@@ -2063,30 +1936,32 @@ hipError_t launch_tiles(const ConvP& p, int cfg, hipStream_t s) {
     case CFG_64x128: return launch_cfg<WT, InT, OutT, BK, 2, 2, 1, 2, 1>(p, s);
     case CFG_128x64: return launch_cfg<WT, InT, OutT, BK, 2, 2, 2, 1, 1>(p, s);
     case CFG_32x256: return launch_cfg<WT, InT, OutT, BK, 1, 4, 1, 2, 1>(p, s);
-    default: return launch_cfg<WT, InT, OutT, BK, 2, 2, 1, 1, 1>(p, s);
+    case CFG_64x64: return launch_cfg<WT, InT, OutT, BK, 2, 2, 1, 1, 1>(p, s);
+    default: return hipErrorInvalidValue;
     }
 }
 
 template <typename WT, typename OutT>
-hipError_t launch_halo_dispatch(const ConvP& p, const ftc_op& o, hipStream_t s) {
-    const int sn = halo_sn(o), cpr = halo_cpr(o);
-    if constexpr (sizeof(WT) == 2 && sizeof(OutT) == 2) {
-        if (hint_wl1(o) && (o.flags & FTC_FLAG_W_FRAG) && cpr == 8 && sn == 3) {
-            const bool up = (o.flags & FTC_FLAG_UPCAT_IN) != 0;
-            if (o.flags & FTC_FLAG_TOP_FUSE) return up ? launch_wl1<WT, OutT, true, true>(p, s) : launch_wl1<WT, OutT, true, false>(p, s);
-            return up ? launch_wl1<WT, OutT, false, true>(p, s) : launch_wl1<WT, OutT, false, false>(p, s);
-        }
-    }
-    if (o.flags & FTC_FLAG_TOP_FUSE) {
+hipError_t launch_halo_dispatch(const ConvP& p, const ConvChoice& c, hipStream_t s) {
+    const int sn = c.halo_sn, cpr = c.halo_cpr;
+    const bool up = c.upcat_in;
+    if (c.family == CONV_WL1) {
         if constexpr (sizeof(WT) == 2 && sizeof(OutT) == 2) {
-            if (cpr == 8 && sn == 3) return (o.flags & FTC_FLAG_UPCAT_IN) ? launch_halo<WT, OutT, 8, 3, true, true>(p, s) : launch_halo<WT, OutT, 8, 3, true>(p, s);
-        }
-        if constexpr (sizeof(WT) == 4 && sizeof(OutT) == 4) {                  // fp32 / fp16x3: the FMA epilogue (conv_epilogue_topfuse_f32)
-            if (cpr == 8 && sn == 3) return (o.flags & FTC_FLAG_UPCAT_IN) ? launch_halo<WT, OutT, 8, 3, true, true>(p, s) : launch_halo<WT, OutT, 8, 3, true>(p, s);
+            if (cpr == 8 && sn == 3) {
+                if (c.top_fuse) return up ? launch_wl1<WT, OutT, true, true>(p, s) : launch_wl1<WT, OutT, true, false>(p, s);
+                return up ? launch_wl1<WT, OutT, false, true>(p, s) : launch_wl1<WT, OutT, false, false>(p, s);
+            }
         }
         return hipErrorInvalidValue;
     }
-    if (o.flags & FTC_FLAG_UPCAT_IN) {
+    if (c.top_fuse) {
+        // 16 bit: the MFMA epilogue; fp32 / fp16x3: the FMA epilogue (conv_epilogue_topfuse_f32)
+        if constexpr (sizeof(WT) == sizeof(OutT)) {
+            if (cpr == 8 && sn == 3) return up ? launch_halo<WT, OutT, 8, 3, true, true>(p, s) : launch_halo<WT, OutT, 8, 3, true>(p, s);
+        }
+        return hipErrorInvalidValue;
+    }
+    if (up) {
         if constexpr (sizeof(WT) == 2 && sizeof(OutT) == 2) {
             if (sn == 3) return cpr == 8 ? launch_halo<WT, OutT, 8, 3, false, true>(p, s) : launch_halo<WT, OutT, 4, 3, false, true>(p, s);
         }
@@ -2098,58 +1973,42 @@ hipError_t launch_halo_dispatch(const ConvP& p, const ftc_op& o, hipStream_t s) 
     if (cpr == 8) {
         if (sn == 3) return launch_halo<WT, OutT, 8, 3>(p, s);
         if (sn == 2) return launch_halo<WT, OutT, 8, 2>(p, s);
-        return launch_halo<WT, OutT, 8, 1>(p, s);
+        if (sn == 1) return launch_halo<WT, OutT, 8, 1>(p, s);
     }
     if constexpr (sizeof(WT) == 2) {
-        if (sn == 3) return launch_halo<WT, OutT, 4, 3>(p, s);
-        if (sn == 2) return launch_halo<WT, OutT, 4, 2>(p, s);
-        return launch_halo<WT, OutT, 4, 1>(p, s);
+        if (cpr == 4) {
+            if (sn == 3) return launch_halo<WT, OutT, 4, 3>(p, s);
+            if (sn == 2) return launch_halo<WT, OutT, 4, 2>(p, s);
+            if (sn == 1) return launch_halo<WT, OutT, 4, 1>(p, s);
+        }
     }
     return hipErrorInvalidValue;
 }
 
-// The instantiations of one type combination fall into four independent parts (halo kernels; tiles with K step 32 / 64 / 128),
-// so that the two heavy combinations can be compiled as four translation units each (conv_igemm_part.hip).
-enum { PART_HALO = 0, PART_BK32 = 1, PART_BK64 = 2, PART_BK128 = 3 };
-
-template <typename WT, typename InT>
-int conv_part(const ftc_op& o) {
-    if constexpr (sizeof(WT) == sizeof(InT)) {
-        if (uses_halo(o)) return PART_HALO;
-    }
-    if constexpr (sizeof(WT) == 2) {
-        const int bk = select_bk(o);
-        if constexpr (sizeof(InT) == 2) {
-            if (bk == 128) return PART_BK128;
-        }
-        if (bk >= 64) return PART_BK64;
-    }
-    return PART_BK32;
-}
-
+// One part (ConvChoice::part) of one type combination: the halo kernels, or the tiles of one K step.
 template <typename WT, typename InT, typename OutT, int PART>
-hipError_t launch_part(const ConvP& p, const ftc_op& o, hipStream_t s) {
+hipError_t launch_part(const ConvP& p, const ConvChoice& c, hipStream_t s) {
     if constexpr (PART == PART_HALO) {
-        if constexpr (sizeof(WT) == sizeof(InT)) return launch_halo_dispatch<WT, OutT>(p, o, s);
+        if constexpr (sizeof(WT) == sizeof(InT)) return launch_halo_dispatch<WT, OutT>(p, c, s);
         else return hipErrorInvalidValue;
     } else if constexpr (PART == PART_BK128) {
-        if constexpr (sizeof(WT) == 2 && sizeof(InT) == 2) return launch_tiles<WT, InT, OutT, 128>(p, select_cfg(o), s);
+        if constexpr (sizeof(WT) == 2 && sizeof(InT) == 2) return launch_tiles<WT, InT, OutT, 128>(p, c.cfg, s);
         else return hipErrorInvalidValue;
     } else if constexpr (PART == PART_BK64) {
-        if constexpr (sizeof(WT) == 2) return launch_tiles<WT, InT, OutT, 64>(p, select_cfg(o), s);
+        if constexpr (sizeof(WT) == 2) return launch_tiles<WT, InT, OutT, 64>(p, c.cfg, s);
         else return hipErrorInvalidValue;
     } else {
-        return launch_tiles<WT, InT, OutT, 32>(p, select_cfg(o), s);
+        return launch_tiles<WT, InT, OutT, 32>(p, c.cfg, s);
     }
 }
 
 template <typename WT, typename InT, typename OutT>
-hipError_t launch_types(const ConvP& p, const ftc_op& o, hipStream_t s) {
-    switch (conv_part<WT, InT>(o)) {
-    case PART_HALO: return launch_part<WT, InT, OutT, PART_HALO>(p, o, s);
-    case PART_BK128: return launch_part<WT, InT, OutT, PART_BK128>(p, o, s);
-    case PART_BK64: return launch_part<WT, InT, OutT, PART_BK64>(p, o, s);
-    default: return launch_part<WT, InT, OutT, PART_BK32>(p, o, s);
+hipError_t launch_types(const ConvP& p, const ConvChoice& c, hipStream_t s) {
+    switch (c.part) {
+    case PART_HALO: return launch_part<WT, InT, OutT, PART_HALO>(p, c, s);
+    case PART_BK128: return launch_part<WT, InT, OutT, PART_BK128>(p, c, s);
+    case PART_BK64: return launch_part<WT, InT, OutT, PART_BK64>(p, c, s);
+    default: return launch_part<WT, InT, OutT, PART_BK32>(p, c, s);
     }
 }
 

@@ -12,6 +12,6 @@
 #define FTC_PART_W __bf16
 #endif
 
-hipError_t FTC_PART_FN(const convimpl::ConvP& p, const ftc_op& o, hipStream_t s) {
-    return convimpl::launch_part<FTC_PART_W, FTC_PART_W, FTC_PART_OUT, FTC_PART>(p, o, s);
+hipError_t FTC_PART_FN(const convimpl::ConvP& p, const convimpl::ConvChoice& c, hipStream_t s) {
+    return convimpl::launch_part<FTC_PART_W, FTC_PART_W, FTC_PART_OUT, FTC_PART>(p, c, s);
 }

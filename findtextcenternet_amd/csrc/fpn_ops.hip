@@ -269,14 +269,6 @@ hipError_t launch_nms(const OpArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// FTC_OP_CONV, 3x3 stride 1, fp32 in / out / weights (plain or fp16x3 pre-split), 1..4 output channels, no activation / residual / gate
-bool ftc_thin_conv_legal(const ftc_op& o) {
-    return o.ksize == 3 && o.stride == 1 && o.Cout >= 1 && o.Cout <= 4 && o.in_dtype == FTC_F32 && o.out_dtype == FTC_F32 && o.w_dtype == FTC_F32 &&
-           o.act == FTC_ACT_NONE && o.Cin % 32 == 0 && o.Cin_total == o.Cin && o.cin_off == 0 && o.H == o.Ho && o.W == o.Wo &&
-           !(o.flags & (FTC_FLAG_RESIDUAL | FTC_FLAG_SE_SCALE | FTC_FLAG_BORDER_BIAS | FTC_FLAG_W_PER_IMAGE | FTC_FLAG_UPCAT_IN | FTC_FLAG_TOP_FUSE | 0x100)) &&
-           (long)o.H * o.W * o.Cin * 4 < 0x7ff00000L;
-}
-
 hipError_t launch_thin_conv(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
     const int G = o.groups > 1 ? o.groups : 1;

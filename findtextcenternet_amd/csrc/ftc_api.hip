@@ -2,8 +2,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
+#include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ftc_common.h"
@@ -33,6 +36,36 @@ hipError_t launch_gather_rows(const float* feat, const int32_t* sel_index, const
 hipError_t launch_losses(const float* heat, const long* hstrides, const float* label, const int32_t* idmap, int B, int h, int w, const float* const* dec,
                          const int* mod, const int32_t* sel_index, const int32_t* count, long cap, float* out, void* scratch, hipStream_t s);
 hipError_t launch_cov_step(const float* L, int n, int iter, float* state, float* out_loss, hipStream_t s);
+
+// Per-device launch state shared by the launchers (ftc_host.h).  One lock for both: taken for a set / vector lookup per launch, never contended
+// in a single-threaded host loop; a first launch makes its HIP call under it, so a racing thread launches only after the attribute is set.
+namespace {
+std::mutex g_dev_mu;
+std::set<std::pair<const void*, int>> g_lds_allowed;      // (kernel, device ordinal)
+std::vector<int> g_dev_cus;                                // [device ordinal], 0 = not asked yet
+}  // namespace
+
+hipError_t ftc_allow_dyn_lds(const void* kernel, int bytes) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(g_dev_mu);
+    if (g_lds_allowed.count({kernel, dev})) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) g_lds_allowed.insert({kernel, dev});
+    return e;
+}
+
+hipError_t ftc_device_cus(int* n_cu) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(g_dev_mu);
+    if (dev >= (int)g_dev_cus.size()) g_dev_cus.resize(dev + 1, 0);
+    if (g_dev_cus[dev] == 0 && (e = hipDeviceGetAttribute(&g_dev_cus[dev], hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
+    *n_cu = g_dev_cus[dev];
+    return hipSuccess;
+}
 
 namespace {
 // FTC_OP_LOSSES: ftc_losses on the NHWC [B,H,W,9] map block of the training plan
@@ -526,14 +559,13 @@ int ftc_op_kernel_label(const ftc_op* op, char* buf, int len) {
     case FTC_OP_STEM: std::snprintf(buf, len, "stem_kernel"); break;
     case FTC_OP_CONV: conv_kernel_label(*op, buf, len); break;
     case FTC_OP_DWCONV:
-        if (op->stride == 1 && !(op->flags & 0x100) && (ftc_is16(op->in_dtype) ? op->act != FTC_ACT_NONE : op->Cin % 4 == 0))
-            std::snprintf(buf, len, "dwconv_strip_kernel<%s,s1>", ftc_dtname(op->in_dtype));
+        if (ftc_dwconv_strip(*op)) std::snprintf(buf, len, "dwconv_strip_kernel<%s,s1>", ftc_dtname(op->in_dtype));
         else std::snprintf(buf, len, "dwconv_kernel<%s,s%d>", ftc_dtname(op->in_dtype), op->stride);
         break;
     case FTC_OP_SE: std::snprintf(buf, len, (op->flags & FTC_FLAG_SE_HPART) ? "se_gate" : "se_fc1+se_fc2"); break;
     case FTC_OP_MBHEAD:     // two instantiations, as the profiler sees them: the whole 24x24 map (FAST) / the general kernel (bands of rows)
         std::snprintf(buf, len, "mbconv_slice<%s,%dch,%s>", op->in_dtype == FTC_F32 ? "f16x3" : ftc_dtname(op->in_dtype), ftc_mbhead_slice(*op),
-                      op->H == 24 && op->W == 24 && op->aux1 == 0 && !(op->flags & 0x100) ? "24x24" : "bands");
+                      ftc_mbhead_whole_map(*op) ? "24x24" : "bands");
         break;
     case FTC_OP_FMBCONV: ftc_fmbconv_label(*op, buf, len); break;
     case FTC_OP_UPCAT: std::snprintf(buf, len, "upcat_kernel<%s>", ftc_dtname(op->in_dtype)); break;

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/ftc.h"
+#include "conv_choice.h"
 
 struct ftc_plan {
     std::vector<ftc_op> ops;
@@ -27,7 +28,19 @@ int ftc_mbhead_slice(const ftc_op& o);          // expanded channels per workgro
 bool ftc_fmbconv_legal(const ftc_op& o);
 
 // conv_igemm.hip: NULL if the convolution op (incl. its tuned kernel choice ftc_op.aux0) is supported, else the reason
+// (conv_choice.h: the choice itself, and conv_pinned_choice / conv_small_tile_choice, which write one back into aux0)
 const char* conv_validate(const ftc_op& op);
+
+// ftc_api.hip: opt-in of `kernel` to `bytes` (> 64 KB) of dynamic LDS, made once per (kernel, device): looks up the calling thread's
+// current device, so it holds when that changes and when host threads race on a first launch; afterwards its only HIP call is hipGetDevice.
+hipError_t ftc_allow_dyn_lds(const void* kernel, int bytes);
+// ftc_api.hip: compute units of the current device (asked once per device)
+hipError_t ftc_device_cus(int* n_cu);
+
+// Kernel picks that ftc_op_kernel_label restates: one predicate each, called by the launcher and by the label
+bool ftc_dwconv_strip(const ftc_op& o);         // backbone_ops.hip: FTC_OP_DWCONV runs the stride-1 strip kernel
+bool ftc_mbhead_whole_map(const ftc_op& o);     // mbconv_slice.hip: FTC_OP_MBHEAD runs the whole-24x24-map instantiation (both forms)
+int ftc_fmbconv_bk(const ftc_op& o);            // fused_mbconv.hip: K step of the 16-bit FTC_OP_FMBCONV kernel
 
 // page_merge.hip: the header block in the scratch of the rank-ordered page selections (ftc_page_merge; ftc_page_fill in page_fill.hip) and the two
 // of its kernels both use -- the exclusive prefix sum of the neighbour counts (more edges than `cap`: use_seq = 1) and the kept ranks -> keep_idx
@@ -41,8 +54,3 @@ hipError_t launch_page_finish(const float* loc, const int* keep_idx, const int* 
 // glyph_select.hip: the per-glyph code-point selection kernel behind ftc_glyph_select / ftc_glyph_decode (arguments validated by the caller)
 hipError_t ftc_glyph_select_launch(const float* l0, const float* l1, const float* l2, int64_t ld0, int64_t ld1, int64_t ld2, int n,
                                    float* s0, float* s1, float* s2, int64_t* ids, float* probs, hipStream_t stream);
-// conv_igemm.hip: aux0 with the kernel choice the op would run with made explicit (tile config, staging, K step), split-K dropped
-int conv_pinned_choice(const ftc_op& op);
-// conv_igemm.hip: the aux0 of the 64-channel x 64-pixel tile with everything else left to the heuristics (a GEMM with few rows fills more
-// CUs with it)
-int conv_small_tile_choice();

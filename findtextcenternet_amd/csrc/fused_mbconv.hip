@@ -277,12 +277,7 @@ hipError_t launch_fmb(FmbP p, hipStream_t s) {
     using GM = FmbGeom<BK, SN, WM, NBUF, SMT>;
     auto kern = fmbconv_fused_kernel<T, BK, SN, WM, NBUF, SMT>;
     p.nblk = (p.M + GM::TM - 1) / GM::TM;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, GM::LDS);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(kern), GM::LDS); e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(p.nblk), dim3(GM::NT), GM::LDS, s, p);
     return hipGetLastError();
 }
@@ -505,12 +500,7 @@ __global__ __launch_bounds__(FmbX3::NT, 2) void fmbconv_fused_x3_kernel(const Fm
 }
 
 static hipError_t launch_fmb_x3(FmbP p, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fmbconv_fused_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FmbX3::LDS);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(fmbconv_fused_x3_kernel), FmbX3::LDS); e != hipSuccess) return e;
     p.nblk = (p.M + FmbX3::TM - 1) / FmbX3::TM;
     hipLaunchKernelGGL(fmbconv_fused_x3_kernel, dim3(p.nblk), dim3(FmbX3::NT), FmbX3::LDS, s, p);
     return hipGetLastError();
@@ -534,9 +524,11 @@ bool ftc_fmbconv_legal(const ftc_op& o) {
            (!(o.flags & FTC_FLAG_RESIDUAL) || o.res_dtype == FTC_F32) && px * o.Cin * 2 < 0x7fffffffL && px > 0 && px < 0x7fffffffL / 128;
 }
 
+int ftc_fmbconv_bk(const ftc_op& o) { return o.Cin % 64 == 0 ? 64 : 32; }
+
 const char* ftc_fmbconv_label(const ftc_op& o, char* buf, int len) {
     if (o.w_dtype == FTC_F32) std::snprintf(buf, len, "fmbconv_fused<f16x3,e=%d,bk=32>", o.aux1);
-    else std::snprintf(buf, len, "fmbconv_fused<%s,e=%d,bk=%d>", o.w_dtype == FTC_F16 ? "f16" : "bf16", o.aux1, o.Cin % 64 == 0 ? 64 : 32);
+    else std::snprintf(buf, len, "fmbconv_fused<%s,e=%d,bk=%d>", o.w_dtype == FTC_F16 ? "f16" : "bf16", o.aux1, ftc_fmbconv_bk(o));
     return buf;
 }
 
@@ -559,7 +551,7 @@ hipError_t launch_fmbconv(const OpArgs& a, hipStream_t s) {
         p.nk = 9 * p.ncb;
         return launch_fmb_x3(p, s);
     }
-    const int bk = o.Cin % 64 == 0 ? 64 : 32;
+    const int bk = ftc_fmbconv_bk(o);
     p.ncb = o.Cin / bk;
     p.nk = 9 * p.ncb;
     p.nblk = 0;

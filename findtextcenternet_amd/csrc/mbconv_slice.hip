@@ -363,6 +363,9 @@ int ftc_mbhead_band_rows(int H, int W) {
     return r - 2 > 0 ? r - 2 : -1;
 }
 
+// the FAST instantiation holds the whole 24x24 map in one workgroup (one band).  0x100: the general kernel (tests)
+bool ftc_mbhead_whole_map(const ftc_op& o) { return o.H == 24 && o.W == 24 && ftc_mbhead_bands(o) == 1 && !(o.flags & 0x100); }
+
 hipError_t launch_mbhead_x3(const OpArgs& a, hipStream_t s);
 
 hipError_t launch_mbhead(const OpArgs& a, hipStream_t s) {
@@ -379,25 +382,17 @@ hipError_t launch_mbhead(const OpArgs& a, hipStream_t s) {
     p.inv_hw = 1.0f / (float)(o.H * o.W);
     p.tl = (o.flags & 0x1000) ? reinterpret_cast<unsigned long long*>(const_cast<void*>(a.in2)) : nullptr;      // phase timeline (tools/mbslice_bench.py)
     const int slice = ftc_mbhead_slice(o);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipSuccess;
-        for (const void* f : {reinterpret_cast<const void*>(mbconv_slice_kernel<__bf16, true, 4>), reinterpret_cast<const void*>(mbconv_slice_kernel<__bf16, false, 4>),
-                              reinterpret_cast<const void*>(mbconv_slice_kernel<_Float16, true, 4>), reinterpret_cast<const void*>(mbconv_slice_kernel<_Float16, false, 4>)})
-            if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, MsGeom<4>::LDS);
-        for (const void* f : {reinterpret_cast<const void*>(mbconv_slice_kernel<__bf16, true, 3>), reinterpret_cast<const void*>(mbconv_slice_kernel<__bf16, false, 3>),
-                              reinterpret_cast<const void*>(mbconv_slice_kernel<_Float16, true, 3>), reinterpret_cast<const void*>(mbconv_slice_kernel<_Float16, false, 3>)})
-            if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, MsGeom<3>::LDS);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
     const int nblk = o.B * p.nb * (o.Cout / slice);
-    const bool fast = o.H == 24 && o.W == 24 && p.nb == 1 && !(o.flags & 0x100);          // 0x100: the general kernel (tests)
-#define MBS_LAUNCH(T, F, N) hipLaunchKernelGGL((mbconv_slice_kernel<T, F, N>), dim3(nblk), dim3(MS_NT), MsGeom<N>::LDS, s, p)
+    const bool fast = ftc_mbhead_whole_map(o);
+    hipError_t e = hipSuccess;
+#define MBS_LAUNCH(T, F, N) do {                                                                                                   \
+        if ((e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(mbconv_slice_kernel<T, F, N>), MsGeom<N>::LDS)) == hipSuccess) \
+            hipLaunchKernelGGL((mbconv_slice_kernel<T, F, N>), dim3(nblk), dim3(MS_NT), MsGeom<N>::LDS, s, p);                  \
+    } while (0)
 #define MBS_PICK(T, N) do { if (fast) MBS_LAUNCH(T, true, N); else MBS_LAUNCH(T, false, N); } while (0)
     if (o.in_dtype == FTC_F16) { if (slice == 96) MBS_PICK(_Float16, 3); else MBS_PICK(_Float16, 4); }
     else { if (slice == 96) MBS_PICK(__bf16, 3); else MBS_PICK(__bf16, 4); }
 #undef MBS_PICK
 #undef MBS_LAUNCH
-    return hipGetLastError();
+    return e != hipSuccess ? e : hipGetLastError();
 }

@@ -346,16 +346,9 @@ hipError_t launch_mbhead_x3(const OpArgs& a, hipStream_t s) {
     p.presplit_out = (o.flags & FTC_FLAG_PRESPLIT) ? 1 : 0;
     p.img_bytes = (unsigned)((long)o.H * o.W * o.Cin * 4);
     p.inv_hw = 1.0f / (float)(o.H * o.W);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mbconv_slice_x3_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(mbconv_slice_x3_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
     const int nblk = o.B * p.nb * (o.Cout / X3_CC);
-    const bool fast = o.H == 24 && o.W == 24 && p.nb == 1 && !(o.flags & 0x100);
-    if (fast) hipLaunchKernelGGL(mbconv_slice_x3_kernel<true>, dim3(nblk), dim3(X3_NT), X3_LDS, s, p);
-    else hipLaunchKernelGGL(mbconv_slice_x3_kernel<false>, dim3(nblk), dim3(X3_NT), X3_LDS, s, p);
+    auto kern = ftc_mbhead_whole_map(o) ? mbconv_slice_x3_kernel<true> : mbconv_slice_x3_kernel<false>;
+    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(kern), X3_LDS); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(nblk), dim3(X3_NT), X3_LDS, s, p);
     return hipGetLastError();
 }

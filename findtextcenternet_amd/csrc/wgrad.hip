@@ -11,6 +11,7 @@
 // fp32 partial tile; wgrad_reduce_kernel sums the splits in a fixed order (deterministic) and ADDS the result to the gradient buffer
 // in the PyTorch layout [Cout][Cin][k][k].
 #include "ftc_common.h"
+#include "ftc_host.h"
 
 namespace {
 
@@ -962,12 +963,10 @@ hipError_t launch_wgrad(const OpArgs& a, hipStream_t s) {
         const dim3 g1((o.Cout + 127) / 128, (o.Cin + 127) / 128, S);
         const size_t lds = (size_t)4 * 32 * 256 * 2;
         if (o.w_dtype == FTC_F16) {
-            static bool set16 = false;
-            if (!set16) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1t_kernel<_Float16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); set16 = true; }
+            (void)ftc_allow_dyn_lds(reinterpret_cast<const void*>(wgrad1t_kernel<_Float16>), (int)lds);
             hipLaunchKernelGGL(wgrad1t_kernel<_Float16>, g1, dim3(256), lds, s, p);
         } else {
-            static bool setb = false;
-            if (!setb) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad1t_kernel<__bf16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); setb = true; }
+            (void)ftc_allow_dyn_lds(reinterpret_cast<const void*>(wgrad1t_kernel<__bf16>), (int)lds);
             hipLaunchKernelGGL(wgrad1t_kernel<__bf16>, g1, dim3(256), lds, s, p);
         }
         hipError_t e1 = hipGetLastError();

@@ -402,3 +402,79 @@ def test_fused_block_switches_change_the_plan_and_it_still_validates(models, mon
             monkeypatch.delenv(k)
         assert sum(pl.ops[i].kind == L.OP_FMBCONV for i in range(len(pl.ops))) == want, env
         assert abs(sum(mm.flops for mm in pl.meta) / key[0] / 1e9 - 865.0006) < 0.01          # the same network either way
+
+
+# ---- the kernel choice of FTC_OP_CONV (csrc/conv_choice.h) -----------------------------------------------------------------------
+
+@pytest.mark.parametrize("part", ["table", "fuzz", "special", "every_aux0"])
+def test_conv_choice_sweep_matches_the_recorded_one(part):
+    """Which (op, aux0) pairs ftc_plan_create accepts, the full error text of the others and every kernel label, entry by entry against
+    tests/golden/conv_choices.json.gz (written by tests/conv_choice_sweep.py --write before the choice moved into conv_resolve)."""
+    import conv_choice_sweep as S
+    gold = S.load_golden()
+    want = gold["parts"][part]
+    got = S.replay(part)
+    assert len(got) == len(want)
+    ents = S.entries(part)
+    for i, ((lab, err), (li, ei)) in enumerate(zip(got, want)):
+        assert (lab, err) == (gold["labels"][li], None if ei < 0 else gold["errors"][ei]), (part, i, ents[i])
+    assert sum(err is None for _, err in got) == {"table": 4186, "fuzz": 943, "special": 241, "every_aux0": 191 + 263 + 247 + 389 + 95}[part]
+
+
+def test_conv_choice_of_every_op_of_the_xl_plans_matches_the_recorded_one(sd, models):
+    """(kind, aux0, label) of every op of the xl plans at 768 x 768 in the modes and batch sizes bench.py and the GPU suite run."""
+    import conv_choice_sweep as S
+    gold = S.load_golden()
+    ms = dict(models)
+    for mode, B in S.PLAN_CASES:
+        if mode not in ms:
+            ms[mode] = FtcModel(sd, mode)
+        want = [[k, a, gold["labels"][li]] for k, a, li in gold["plans"][f"{mode}_b{B}"]]
+        assert S.plan_entries(ms[mode], B) == want, (mode, B)
+
+
+def test_an_explicit_hint_is_the_kernel_the_label_names():
+    """The contract between tuning.candidates and the library: for every (op, hint) pair of the table and fuzz sweeps that ftc_plan_create accepts, the label names the
+    family, tile, K step, ring depth and split-K that tuning.describe(hint) names.  The two kernels without variants (thin_conv3x3, conv3x3_c32) take their ops
+    whatever the hint says."""
+    import conv_choice_sweep as S
+    bad, n = [], 0
+    for part in ("table", "fuzz"):
+        for f, aux0 in S.entries(part):
+            if aux0 == 0:
+                continue
+            lab, err = S.verdict(S.make_op(dict(f, aux0=aux0)))
+            if err is not None or lab.startswith(("thin_conv3x3<", "conv3x3_c32<")):
+                continue
+            n += 1
+            d = dict(kv.split("=") for kv in tuning.describe(aux0).split(",") if "=" in kv)
+            if tuning.describe(aux0).startswith("halo"):
+                ok = lab.startswith("conv3x3_halo<") and f",tile={d['channels']}x16x16," in lab and (d.get("bk") != "32" or lab.endswith(",bk=32>"))
+            elif tuning.describe(aux0).startswith("px144"):
+                ok = lab.startswith("conv1x1_px144<") and f",tile={d['tile']}," in lab
+            else:
+                ring = {"reg": 1, "dma2": 2, "dma3": 3}[d["stage"]]
+                ok = (lab.startswith("conv_igemm_glds<" if ring > 1 else "conv_igemm<") and f",tile={d['tile']},bk={d['bk']},nbuf={ring}" in lab and
+                      (f",splitk={d['splitk']}>" in lab if "splitk" in d else "splitk" not in lab))
+            if not ok:
+                bad.append((tuning.describe(aux0), lab))
+    assert n > 4000 and not bad, (n, len(bad), bad[:5])
+
+
+def test_conv_choice_header_is_host_only_and_clean_under_sanitizers(tmp_path):
+    """csrc/conv_choice.h needs no HIP header: tests/c_abi/conv_choice_host.cc (plain C++, its own main) resolves and labels every aux0 on five ops under
+    AddressSanitizer + UBSan and prints what the library answered for the same entries."""
+    import subprocess
+    import conv_choice_sweep as S
+    exe = str(tmp_path / "conv_choice_host")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "c_abi", "conv_choice_host.cc"), "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    gold = S.load_golden()
+    lines = r.stdout.splitlines()
+    want = gold["parts"]["every_aux0"]
+    assert len(lines) == len(want)
+    for line, (li, ei) in zip(lines, want):
+        why, lab = line.split("\t")
+        assert lab == gold["labels"][li] and (why == "" if ei < 0 else gold["errors"][ei].endswith(why) and why != ""), (line, gold["labels"][li], ei)
