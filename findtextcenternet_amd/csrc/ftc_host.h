@@ -1,4 +1,4 @@
-// Host-side definitions shared by the C-ABI translation units (ftc_api.hip, model.hip).
+// Host-side definitions shared by the C-ABI translation units (ftc_api.hip; pack.hip, plan.hip and model.hip through model_net.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

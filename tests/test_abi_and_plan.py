@@ -349,12 +349,11 @@ def test_fp16x3_plans_build_with_every_documented_switch(sd, monkeypatch):
     pre-split operands (any of the switches below) used to inherit a 144-pixel-tile hint that is only legal with them, and
     ftc_plan_create refused the whole batch-8 / batch-32 plan.  apply_tuning now adopts a hint only if the op validates with it."""
     m = FtcModel(sd, "fp16x3")
-    cases = [({"FTC_NO_PRESPLIT": "1"}, 8, False), ({"FTC_NO_MBSLICE_X3": "1"}, 8, True), ({"FTC_NO_MBSLICE": "1"}, 32, False),
-             ({"FTC_MBSLICE_MINWG": "1000000"}, 32, True)]
-    for env, B, nchw in cases:                   # (plans are cached per (B, H, W, layout): one key per switch)
+    cases = [({"FTC_NO_PRESPLIT": "1"}, 8), ({"FTC_NO_MBSLICE_X3": "1"}, 8), ({"FTC_NO_MBSLICE": "1"}, 32), ({"FTC_MBSLICE_MINWG": "1000000"}, 32)]
+    for env, B in cases:                         # (the plan cache is keyed by the switches: the same shape under each)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        pl = m.plan(B, 768, 768, nchw=nchw)
+        pl = m.plan(B, 768, 768)
         for k in env:
             monkeypatch.delenv(k)
         px = [i for i in range(len(pl.ops)) if pl.ops[i].kind == L.OP_CONV and 8 <= (pl.ops[i].aux0 & 15) <= 11 and not pl.ops[i].aux0 & 64]
@@ -392,12 +391,13 @@ def test_round6_kernels_are_selected_by_the_plans_that_bench_runs(sd, models):
 
 def test_fused_block_switches_change_the_plan_and_it_still_validates(models, monkeypatch):
     """FTC_NO_FMBFUSE=1 keeps the two-launch form of the Fused-MBConv blocks, FTC_FMBFUSE_ALL=1 also fuses stage 3 (measured slower):
-    both plans build and pass ftc_plan_create's validation (plans are cached per (B, H, W, layout): one key per switch)."""
+    both plans build and pass ftc_plan_create's validation."""
     m = models["bf16"]
-    for env, key, want in (({"FTC_NO_FMBFUSE": "1"}, (4, 768, 768, False), 0), ({"FTC_FMBFUSE_ALL": "1"}, (4, 768, 768, True), 14), ({}, (5, 768, 768, False), 7)):
+    key = (4, 768, 768)                          # (the plan cache is keyed by the switches: one shape under all three settings)
+    for env, want in (({"FTC_NO_FMBFUSE": "1"}, 0), ({"FTC_FMBFUSE_ALL": "1"}, 14), ({}, 7)):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
-        pl = m.plan(key[0], key[1], key[2], nchw=key[3])
+        pl = m.plan(*key)
         for k in env:
             monkeypatch.delenv(k)
         assert sum(pl.ops[i].kind == L.OP_FMBCONV for i in range(len(pl.ops))) == want, env
@@ -478,3 +478,65 @@ def test_conv_choice_header_is_host_only_and_clean_under_sanitizers(tmp_path):
     for line, (li, ei) in zip(lines, want):
         why, lab = line.split("\t")
         assert lab == gold["labels"][li] and (why == "" if ei < 0 else gold["errors"][ei].endswith(why) and why != ""), (line, gold["labels"][li], ei)
+
+
+# ---- plan construction and weight packing against the recorded ones (tests/plan_sweep.py) ----------------------------------------
+
+@pytest.fixture(scope="module")
+def plan_replay():
+    """(recorded, replayed): tests/golden/model_plans.json.gz, written by `tests/plan_sweep.py --write` from the library of the commit before the
+    plan builder was split up, and the same cases from the library in the tree.  The sweep builds its own models -- the xl ones from the checkpoint
+    WITH the decoder, which the `models` fixture above does not carry.  The plan cache is keyed by the switches, so every switch case of a mode
+    runs on the one xl model of that mode."""
+    import plan_sweep as S
+    return S.load_golden(), S.replay()
+
+
+@pytest.mark.parametrize("part", ["plans", "weights", "decoder"])
+def test_plans_weights_and_decoder_workspaces_equal_the_recorded_ones(plan_replay, part):
+    """plans: every field of every ftc_op (refs and tuned aux0 included), every op's name, kind, flops and bytes and the plan totals, for xl at
+    768 x 768 in four modes and four batch sizes, the other sizes, and every plan switch alone; weights: the sha256 of every MiB of the packed blob
+    of 13 models; decoder: the workspace sizes of the two decoder paths.  Equal plans on equal weights are the same launches on the same data."""
+    import plan_sweep as S
+    want, got = plan_replay
+    assert sorted(got[part]) == sorted(want[part])
+    assert len(want["plans"]) == 94 and len(want["weights"]) == 13 and len(want["decoder"]) == 4
+    assert S.decoder_sizes_missing(want) == [] and S.decoder_sizes_missing(got) == []          # (-1: a model without the decoder compares nothing)
+    diff = S.first_difference(want, got, part)
+    assert diff is None, diff
+
+
+def test_a_plan_difference_is_named_by_case_op_and_field(plan_replay):
+    import copy
+    import plan_sweep as S
+    want, got = plan_replay
+    name = S.case_name("xl", "bf16", 8, 768, 768)
+    bad = {"plans": {name: copy.deepcopy(got["plans"][name])}}
+    bad["plans"][name]["ops"][5][S.RECORD_FIELDS.index("out2.offset")] += 256
+    diff = S.first_difference({"plans": {name: want["plans"][name]}}, bad, "plans")
+    assert diff.startswith(f"plan {name}: op 5 (backbone.features.") and "out2.offset = " in diff, diff
+
+
+def test_every_plan_switch_changes_a_plan_and_an_off_value_does_not(plan_replay):
+    """Each switch differs from the default plan of the same mode and batch in at least one of fp32, bf16 and fp16x3 (in the recorded plans and in
+    the replayed ones: a case that changed nothing would prove nothing), and FTC_NO_MBSLICE=0 / FTC_NO_MBSLICE= (empty) are the default plan."""
+    import plan_sweep as S
+    for doc in plan_replay:
+        assert S.idle_switches(doc) == []
+        base = doc["plans"][S.case_name("xl", "bf16", 8, 768, 768)]
+        for k, v in S.SAME_AS_DEFAULT:
+            assert doc["plans"][S.case_name("xl", "bf16", 8, 768, 768, False, {k: v})] == base, (k, v)
+    minwg1 = plan_replay[1]["plans"][S.case_name("xl", "bf16", 2, 768, 768, False, {"FTC_MBSLICE_MINWG": "1"})]
+    assert minwg1 != plan_replay[1]["plans"][S.case_name("xl", "bf16", 2, 768, 768)]
+
+
+def test_plan_cache_is_keyed_by_the_switches(models, monkeypatch):
+    """A switch set between two requests for the same shape gives the plan of the new setting, and taking it away gives the first plan back."""
+    m = models["bf16"]
+    n_fmb = lambda pl: sum(pl.ops[i].kind == L.OP_FMBCONV for i in range(len(pl.ops)))       # noqa: E731
+    first = m.plan(3, 768, 768)
+    assert n_fmb(first) == 7
+    monkeypatch.setenv("FTC_NO_FMBFUSE", "1")
+    assert n_fmb(m.plan(3, 768, 768)) == 0
+    monkeypatch.delenv("FTC_NO_FMBFUSE")
+    assert m.plan(3, 768, 768).handle == first.handle

@@ -47,7 +47,7 @@ def _write_weights(wpath):
 def test_host_side_of_the_abi_under_asan_ubsan(tmp_path):
     """the host side of the shim -- checkpoint folding / packing for all four precisions, plan building and
     validation for three shapes, op introspection, the bounded decoder-plan cache (eviction), error paths -- built with
-    -fsanitize=address,undefined (tools/build_asan.sh: model.hip + ftc_api.hip instrumented, device code not) and driven by the
+    -fsanitize=address,undefined (tools/build_asan.sh: pack.hip, plan.hip, model.hip + ftc_api.hip instrumented, device code not) and driven by the
     host-only C client tests/c_abi/ftc_c_host_check.c.  No device is touched: runs in the build container."""
     import shutil
     if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
