@@ -518,7 +518,7 @@ __global__ __launch_bounds__(256) void se_fc2_fold64_kernel(const float* __restr
 
 // FOLD for the fp16x3 mode (FTC_FLAG_SPLIT16; the fp32 plan): the project weights are stored PRE-SPLIT -- every 16-byte chunk of four
 // fp32 weights as [hi x4 | lo x4] IEEE halves (model.hip add_compute) -- so the folded per-image copy is too: w = hi + lo (exact in fp32),
-// w * scale, split again (same split as conv_igemm_impl.h chunk_hl).  With it the project convolution of the fp16x3 plan streams both
+// w * scale, clamped and split again (same split as conv_igemm_impl.h chunk_hl).  With it the project convolution of the fp16x3 plan streams both
 // operands by DMA like the 16-bit plans do, instead of gating every activation element while staging it (87 us per stage-6 block).
 // Same prologue as se_fc2_fold64_kernel (64 channels per workgroup); 16 lanes x one chunk = the 64 channels, 16 rows per pass.
 __global__ __launch_bounds__(256) void se_fc2_foldx3_kernel(const float* __restrict__ hidden, const float* __restrict__ w2t,
@@ -573,8 +573,8 @@ __global__ __launch_bounds__(256) void se_fc2_foldx3_kernel(const float* __restr
         h4 oh, ol;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float x = ((float)hi[e] + (float)lo[e]) * f[e];
-            const _Float16 hh = (_Float16)f16_sat(x);
+            const float x = f16_sat(((float)hi[e] + (float)lo[e]) * f[e]);
+            const _Float16 hh = (_Float16)x;
             oh[e] = hh;
             ol[e] = (_Float16)(x - (float)hh);
         }

@@ -114,17 +114,21 @@ __device__ __forceinline__ f32x16 mfma16(f16x8 a, f16x8 b, f32x16 c) { return __
 
 // FTC_FLAG_SPLIT16 ("fp16x3": fp32 tensors, weights and accumulation; the products on the 16-bit matrix pipe).  Two fp32 fragments of
 // four K values (two K groups of the fp32 kernels: the lower half-wave holds k = 0..3 | 8..11, the upper 4..7 | 12..15 -- the same
-// permutation on both operands) become the hi / lo halves of ONE 32x32x16 operand: hi = fp16(x) (clamped to the format's range),
-// lo = fp16(x - hi): 22 significand bits.  A.B ~= Ahi.Blo + Alo.Bhi + Ahi.Bhi (the dropped lo.lo term is 2^-24 relative): 3 MFMAs of
-// 32 cycles for 16 K values instead of 8 fp32 MFMAs of 64 cycles.
+// permutation on both operands) become the hi / lo halves of ONE 32x32x16 operand.  The split (spec and CPU model: tests/x3_model.py):
+// xs = clamp(x, +-65504), hi = fp16(xs), lo = fp16(xs - hi) -- lo from the CLAMPED value, so a value beyond the range behaves exactly as
+// +-65504 does and no inf can arise.  hi + lo carries 22 significand bits where |x| >= 2^-3; below that lo is a subnormal half (gfx950's
+// fp16 MFMAs honour those: tests/test_gpu_x3_range.py) with 2^-24 absolute resolution, i.e. 2^-25 / |x| relative: 18 bits at 0.02, 15 at
+// 1e-3, the 11 bits of hi alone from 2^-13 down.  A.B ~= Ahi.Blo + Alo.Bhi + Ahi.Bhi (the dropped lo.lo term is 2^-24 relative): 3 MFMAs
+// of 32 cycles for 16 K values instead of 8 fp32 MFMAs of 64 cycles.
 __device__ __forceinline__ void split16(const f32x4& a0, const f32x4& a1, f16x8& hi, f16x8& lo) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const _Float16 h0 = (_Float16)f16_sat(a0[e]), h1 = (_Float16)f16_sat(a1[e]);
+        const float s0 = f16_sat(a0[e]), s1 = f16_sat(a1[e]);
+        const _Float16 h0 = (_Float16)s0, h1 = (_Float16)s1;
         hi[e] = h0;
         hi[4 + e] = h1;
-        lo[e] = (_Float16)(a0[e] - (float)h0);
-        lo[4 + e] = (_Float16)(a1[e] - (float)h1);
+        lo[e] = (_Float16)(s0 - (float)h0);
+        lo[4 + e] = (_Float16)(s1 - (float)h1);
     }
 }
 // One 16-byte chunk of four fp32 values <-> the same 16 bytes as [hi x4 | lo x4] IEEE halves ("pre-split" chunk).  The WEIGHTS of an
@@ -135,9 +139,10 @@ __device__ __forceinline__ u32x4 chunk_hl(const f32x4& v) {
     f16x4 h, l;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const _Float16 hh = (_Float16)f16_sat(v[e]);
+        const float vs = f16_sat(v[e]);
+        const _Float16 hh = (_Float16)vs;
         h[e] = hh;
-        l[e] = (_Float16)(v[e] - (float)hh);
+        l[e] = (_Float16)(vs - (float)hh);
     }
     const u32x2 hu = __builtin_bit_cast(u32x2, h), lu = __builtin_bit_cast(u32x2, l);
     return u32x4{hu[0], hu[1], lu[0], lu[1]};

@@ -164,7 +164,8 @@ struct Packer {
                     uint16_t* d = reinterpret_cast<uint16_t*>(dst) + 2 * o;
                     for (int64_t i = 0; i < kpad; i += 4)
                         for (int e = 0; e < 4; ++e) {
-                            const float x = i + e < k ? src[i + e] : 0.0f;
+                            const float x0 = i + e < k ? src[i + e] : 0.0f;
+                            const float x = x0 > 65504.0f ? 65504.0f : x0 < -65504.0f ? -65504.0f : x0;      // the split's spec: clamp first, then hi, then lo
                             const uint16_t hi = f16_rne(x);
                             d[2 * i + e] = hi;
                             d[2 * i + 4 + e] = f16_rne(x - f16_val(hi));

@@ -112,6 +112,9 @@ struct Blob {                       // the packed weights: 256-byte aligned tens
     void add_f32(const std::string& name, const float* v, int64_t n);
     // MFMA compute type: fp32, or bf16 / fp16 (double -> float -> 16 bit, both steps round-to-nearest-even), or pre-split fp16x3 chunks
     void add_compute(const std::string& name, const double* v, int64_t n, int dt);
+    // fp16x3 packing: the first tensor given to add_compute that holds a value which is not finite or lies beyond +-65504.  The split would
+    // clamp it silently (hi = +-65504, lo = 0) where the reference does not: pack_weights refuses the checkpoint and names the tensor.
+    std::string out_of_range;
 };
 
 // ------------------------------------------------------------------------------------------------

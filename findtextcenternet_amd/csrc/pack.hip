@@ -2,6 +2,7 @@
 // [Cout][kh*kw][Cin] re-layout, conversion to the MFMA compute type, one blob (model_net.h: Blob).
 // Host-only code: no kernels here.  Compiled with -ffp-contract=off so the float64 folding is the plain multiply / subtract sequence
 // (no fused rounding differences between builds).
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <thread>
@@ -84,16 +85,21 @@ void Blob::add_compute(const std::string& name, const double* v, int64_t n, int 
     if (dt == FTC_F32) { add_f32(name, v, n); return; }
     if (dt == FTC_PRECISION_F16X3) {                    // fp16x3: every 16-byte chunk of four fp32 weights becomes [hi x4 | lo x4] IEEE halves
         uint16_t* d = reinterpret_cast<uint16_t*>(add(name, n * 4));
+        std::atomic<bool> beyond{false};
         par_for(n, 1024, [&](int64_t b, int64_t en) {
+            bool bad = false;
             for (int64_t i = b; i + 3 < en; i += 4)
                 for (int e = 0; e < 4; ++e) {
-                    float x = (float)v[i + e];
-                    const float xs = x > 65504.0f ? 65504.0f : x < -65504.0f ? -65504.0f : x;
+                    const float x = (float)v[i + e];
+                    bad |= !(std::fabs(x) <= 65504.0f);              // NaN included
+                    const float xs = x > 65504.0f ? 65504.0f : x < -65504.0f ? -65504.0f : x;      // the split's spec: clamp, then hi, then lo of the clamped value
                     const uint16_t h = f32_to_f16_rne(xs);
                     d[2 * i + e] = h;
-                    d[2 * i + 4 + e] = f32_to_f16_rne(x - f16_to_f32(h));
+                    d[2 * i + 4 + e] = f32_to_f16_rne(xs - f16_to_f32(h));
                 }
+            if (bad) beyond = true;
         });
+        if (beyond && out_of_range.empty()) out_of_range = name;
         return;
     }
     uint16_t* d = reinterpret_cast<uint16_t*>(add(name, n * 2));
@@ -406,6 +412,11 @@ int pack_weights(ftc_model* m, Weights& w) {
         }
     }
     if (!ok) return ftc_set_error(FTC_ERR_INVALID, "ftc_create: " + (w.missing.empty() ? std::string("weight packing failed") : w.missing));
+    const auto refuse_range = [&] {
+        return ftc_set_error(FTC_ERR_INVALID, "ftc_create: folded weight tensor '" + bl.out_of_range + "' holds a value that is not finite or lies beyond +-65504: "
+                                              "FTC_PRECISION_F16X3 would clamp it where the reference does not (use FTC_F32 for this checkpoint)");
+    };
+    if (!bl.out_of_range.empty()) return refuse_range();
     // SimpleDecoder (models/detector.py:232-254), optional: three MLPs Linear(100,2048,no bias) -> BatchNorm1d -> GELU -> Linear(2048,2048,
     // no bias) -> BatchNorm1d -> GELU -> Linear(2048, modulo).  Eval-mode BatchNorm1d (eps 1e-5) folds into the Linear before it; a Linear
     // weight [out][in] already is the K-major layout of a 1x1 convolution.  The first layer's K is zero-padded 100 -> 128.
@@ -431,6 +442,7 @@ int pack_weights(ftc_model* m, Weights& w) {
             bl.add_f32(q + ".l2.b", b2->data, mod);
         }
         if (!ok) return ftc_set_error(FTC_ERR_INVALID, "ftc_create: decoder: " + (w.missing.empty() ? std::string("weight packing failed") : w.missing));
+        if (!bl.out_of_range.empty()) return refuse_range();
         m->has_decoder = true;
     }
     return FTC_OK;

@@ -18,6 +18,10 @@ Numeric modes (``precision`` argument, or env ``FTC_PRECISION``):
 ``"bf16"`` (bf16 MFMA with fp32 accumulation, fp32 residual trunk and fp32 outputs -- the speed mode
 BASELINE.json's config 2 names) and ``"fp16"`` (the same plan with IEEE-half operands: same matrix rate,
 11-bit significands, so about 8x closer to the fp32 result; 16-bit activations saturate at +-65504).
+``"fp16x3"`` is the fp32 plan with every product as three fp16 MFMAs of hi / lo split operands: the reference's 1e-3
+tolerance at about twice the fp32 speed.  Its operands carry 22 significand bits only where |x| >= 2^-3 (below that
+2^-25 / |x| relative: 18 bits at 0.02, 15 at 1e-3) and are clamped at +-65504; include/ftc.h ("fp16x3: range") states
+the envelope, tests/test_gpu_x3_range.py holds it.
 """
 from __future__ import annotations
 

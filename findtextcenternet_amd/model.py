@@ -19,7 +19,10 @@ from . import _lib as L
 # numeric modes: fp32 = parity mode (exact-f32 MFMA); bf16 = speed mode (BASELINE config 2); fp16 = the speed-mode plan with IEEE-half
 # operands (same MFMA rate, 3 more mantissa bits: ~8x closer to the fp32 result, activations saturate at +-65504)
 # "fp16x3": the fp32 plan (fp32 tensors, weights, epilogues, accumulation) with every product on the 16-bit matrix pipe as three
-# fp16 MFMAs of hi / lo split operands (FTC_FLAG_SPLIT16, include/ftc.h): the reference's fp32 tolerance at about twice the fp32 speed
+# fp16 MFMAs of hi / lo split operands (FTC_FLAG_SPLIT16, include/ftc.h): the reference's fp32 tolerance at about twice the fp32 speed.
+# The operands carry 22 significand bits only where |x| >= 2^-3; below that lo is a subnormal half and the precision is 2^-25 / |x|
+# (18 bits at 0.02, 15 at 1e-3, 11 from 2^-13 down); values beyond +-65504 are clamped (ftc_create refuses such weights).  The envelope
+# that follows for a checkpoint is stated in include/ftc.h ("fp16x3: range") and held by tests/test_gpu_x3_range.py.
 PRECISIONS = {"fp32": L.F32, "bf16": L.BF16, "fp16": L.F16, "fp16x3": 3}
 TORCH_DTYPE = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16, "fp16x3": torch.float32}
 

@@ -230,7 +230,8 @@ enum {
     FTC_FLAG_SPLIT16 = 0x2000000, /* CONV with fp32 operands (w_dtype = in_dtype = out_dtype = FTC_F32): "fp16x3" arithmetic -- every fp32 operand is
                                   split into hi + lo IEEE halves while the MFMA fragments are read from LDS and a product becomes three
                                   v_mfma_f32_32x32x16_f16 (hi.lo + lo.hi + hi.hi, fp32 accumulation) instead of eight v_mfma_f32_32x32x2_f32:
-                                  22-bit operands at up to 5.3x the fp32 matrix rate.  Tensors, weights, epilogues: those of the fp32 mode */
+                                  22-bit operands (where |x| >= 2^-3; the range clause is at ftc_create, "fp16x3: range") at up to 5.3x the fp32
+                                  matrix rate.  Tensors, weights, epilogues: those of the fp32 mode */
     FTC_FLAG_ACCUM = 0x800000, /* BNBWD / CONV-as-dgrad helpers: the data-gradient output is added to what `out` holds */
     FTC_FLAG_SIDE_STREAM = 0x4000000, /* any op: ftc_plan_run_streams enqueues it on the side stream (after everything issued on the main stream so
                                   far); whoever builds the plan keeps the op's operands alive and unwritten until the next FTC_OP_JOIN */
@@ -361,9 +362,28 @@ typedef struct ftc_model ftc_model;
    NULL), "l", "m", "s" (models/detector.py:131-136); precision: FTC_F32 = parity mode (what the reference computes), FTC_BF16 =
    speed mode (bf16 MFMA, fp32 accumulation / residual trunk / outputs), FTC_F16 = the same plan with IEEE-half operands (same
    matrix rate, 11-bit significands: ~8x closer to the fp32 result than bf16; activations saturate at +-65504).  Fails with FTC_ERR_INVALID naming the first missing
-   or mis-shaped tensor.  The tensors may be freed after the call. */
+   or mis-shaped tensor (and, with FTC_PRECISION_F16X3, the first folded weight tensor outside +-65504: see below).  The tensors may be freed after the call. */
 int ftc_create(const ftc_tensor* tensors, int n_tensors, const char* model_size, int precision, ftc_model** out);
-/* precision may also be FTC_PRECISION_F16X3: the parity-grade fast mode (fp32 everywhere except the multiplier: see FTC_FLAG_SPLIT16) */
+/* precision may also be FTC_PRECISION_F16X3: the parity-grade fast mode (fp32 everywhere except the multiplier: see FTC_FLAG_SPLIT16).
+   fp16x3: range.  Every operand of a product is split as  xs = clamp(x, +-65504), hi = fp16(xs), lo = fp16(xs - hi)  (round to nearest
+   even; one definition for the device split, the host packing, the SE weight re-split and the tests: tests/x3_model.py), and a product
+   is hi.lo + lo.hi + hi.hi with fp32 accumulation.
+     * Beyond +-65504 an ACTIVATION behaves exactly as +-65504 does (no inf, no NaN; tests/test_gpu_x3_range.py::
+       test_activations_beyond_fp16_range_saturate).  A folded WEIGHT that is not finite or lies beyond +-65504 is refused here:
+       FTC_ERR_INVALID naming the tensor (the reference does not clamp; use FTC_F32 for such a checkpoint).
+     * hi + lo carries 22 significand bits only where |x| >= 2^-3.  Below that lo is a subnormal half: 2^-25 / |x| relative, i.e. 18 bits
+       at 0.02, 15 bits at 1e-3, 11 bits from 2^-13 down.  Measured on gfx950: the fp16 MFMAs and the conversions around them HONOUR
+       subnormal halves, in every fp16x3 kernel family and at every scale
+       (tests/test_gpu_x3_range.py::test_every_x3_kernel_agrees_on_one_subnormal_model), so small operands lose precision as stated
+       and not all at once.  Per GEMM, |ideal fp16x3 - float64| / max |out| on kaiming-scale data with the weights * 2^-j: 4.6e-7 (j = 0,
+       median |w| 2e-2), 1.4e-5 (j = 5, 7e-4), 5.1e-4 (j = 10, 2e-5) -- tests/test_x3_split_host.py::test_mode_precision_per_weight_scale.
+     * End to end (model `s`, the seeded checkpoint, trunks of the untapped stages re-gauged by 2^k so that the fp32 reference is
+       bit-identical): the 1e-3 / identical-NMS-mask contract holds for -8 <= k <= +6 and fails at +8 (1.1e-3) and -10 (1.0e-3).  In
+       magnitudes: the folded project weights (median |w| 4e-3 .. 7e-3 at k = 0) may shrink to a median of about 3e-5 .. 6e-5 and the
+       expand weights (6e-2 .. 9e-2) to about 1e-3, with the activations they meet grown by the same factor -- a weight-to-activation
+       ratio 2^6 below the seeded checkpoint's in the worse direction, 2^8 in the other.  A checkpoint whose BN-folded weights sit
+       further down than that is outside what this mode is stated for (tests/test_gpu_x3_range.py::
+       test_gauge_scaled_checkpoint_end_to_end; table in DESIGN.md section 3). */
 void ftc_destroy(ftc_model* model);
 /* The packed weight blob: the caller copies ftc_weights_bytes() bytes from ftc_weights_host() into device memory
    (256-byte aligned) once and passes that address to every ftc_forward. */

@@ -379,3 +379,72 @@ def stride2_dgrad_case(B, H, W, Cin, Cout, wd, seed=0):
     dx = dx.permute(0, 2, 3, 1).contiguous()
     assert_exact_case([w, dz], Cout * 9, [], [(w, wd), (dz, wd)], L.F32, dx)
     return SimpleNamespace(w=w, dz=dz, want=round_out(dx, L.F32))
+
+
+# ---- two-part operands: exact cases on which the lo half of the fp16x3 split is never zero --------------------------------------
+# x = m * 2^-s + n * 2^-(s+11), m from the sets above, n in {-1, +1}: n * 2^-(s+11) is at most half an ulp of fp16(m * 2^-s), and where it is
+# exactly half (|m| = 1 and 2) round-to-nearest-EVEN returns m * 2^-s, whose last significand bit is 0; so hi = fp16(x) = m * 2^-s and
+# lo = x - hi = n * 2^-(s+11), both exactly.  (One exception is excluded: 1 - 2^-11 is itself a half, so for |m| = 1 n has the sign of m.)  Each of the 3K terms a_hi w_lo + a_lo w_hi +
+# a_hi w_hi (tests/x3_model.py; the lo.lo term is dropped by the spec) is dyadic on the grid 2^-(sa+sw+11), and x3_model.assert_exact_x3
+# proves for each case, from the split parts themselves, that every partial sum in any order is an fp32 value: x3_ref64 rounded to fp32
+# is the only right answer.  Scaling the activations by 2^i and the weights by 2^-j keeps all of that true in fp32 while, in fp16, lo and
+# then hi move through the subnormal range to zero (or up to the clamp at 65504): split_hl models it, the proof is redone on the scaled parts.
+
+def _signs(shape, g):
+    return torch.randint(0, 2, tuple(shape), generator=g).float() * 2.0 - 1.0
+
+
+def _two_part(m, g):
+    n = _signs(m.shape, g)
+    n = torch.where(m.abs() == 1.0, torch.sign(m), n)          # 1 - 2^-11 IS a half (eleven ones): for |m| = 1 the second part points away from zero
+    return m + n * 2.0 ** -11
+
+
+def acts2(shape, g):
+    return _two_part(acts(shape, g), g)
+
+
+def weights2(shape, s, g):
+    return _two_part(_WVALS[torch.randint(0, 4, tuple(shape), generator=g)], g) * 2.0 ** -s
+
+
+def two_part_case(B, H, W, Cin, CinT, cin_off, Cout, k, stride, *, residual=False, se=False, per_image=False, seed=0, i=0, j=0, a_full=False,
+                  w_one_part=False, a_one_part=False):
+    """conv_case's sibling for the fp16x3 kernels: two-part operands, activations * 2^i, weights * 2^-j, bias and residual on the product's
+    grid (* 2^(i-j)).  want[flush] is x3_ref64 of the SCALED operands under the hardware model flush_subnormals = flush, in fp32, proved
+    exact under that model.  a_full: the kernel takes the fp32 activation whole (thin_conv3x3); its activations are then one-part, since a
+    product of two two-part numbers carries the lo.lo term that no grid of 2^23 steps holds."""
+    import x3_model as M
+    g = gen(seed)
+    K = Cin * k * k
+    s = shift_for(K)
+    pad = (k - 1) // 2
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    x_full = (acts if (a_full or a_one_part) else acts2)((B, H, W, CinT), g) * 2.0 ** i
+    w = (weights if w_one_part else weights2)((Cout, Cin, k, k), s, g) * 2.0 ** -j
+    bias = small_ints((Cout,), s, g) * 2.0 ** (i - j)
+    res = small_ints((B, Ho, Wo, Cout), s, g) * 2.0 ** (i - j) if residual else None
+    sc = scales((B, Cin), g) if se else None
+    if per_image:
+        w = w[None] * scales((B, 1, Cin, 1, 1), g)
+    x = x_full[..., cin_off:cin_off + Cin]
+    xin = x * sc[:, None, None, :] if se else x
+    addends = [bias] + ([res] if residual else [])
+    want, z = {}, {}
+    for flush in (False, True):
+        zz = M.x3_ref64(xin, w, stride, pad, flush_subnormals=flush, a_full=a_full) + bias.double()
+        if residual:
+            zz = zz + res.double()
+        M.assert_exact_x3(M.x3_terms(xin, w, flush, a_full), stride, pad, addends, zz)
+        z[flush], want[flush] = zz, zz.float()
+    return SimpleNamespace(B=B, H=H, W=W, Ho=Ho, Wo=Wo, Cin=Cin, CinT=CinT, cin_off=cin_off, Cout=Cout, k=k, stride=stride, pad=pad, x_full=x_full, x=x, xin=xin,
+                           w=w, bias=bias, res=res, sc=sc, z=z, want=want, idt=L.F32, wdt=L.F32, odt=L.F32, x3=True, K=K, i=i, j=j, CoutT=Cout, cout_off=0)
+
+
+def two_part_table_case(case, i=0, j=0, **kw):
+    """A row of test_gpu_ops.CONV_CASES / HALO_CASES / SPLITK_CASES in the two-part family (activation forced to NONE)."""
+    import zlib
+    name, B, H, W, Cin, CinT, cin_off, Cout, CoutT, cout_off, k, stride, _act, residual, se = case
+    c = two_part_case(B, H, W, Cin, CinT, cin_off, Cout, k, stride, residual=residual, se=se, seed=zlib.crc32((name + "two-part").encode()) % 100000, i=i, j=j, **kw)
+    c.CoutT, c.cout_off, c.name, c.mname = CoutT, cout_off, name, "f32x3"
+    return c

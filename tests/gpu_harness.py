@@ -92,9 +92,10 @@ def tdtype(d: int) -> torch.dtype:
 
 def presplit_f16x3(w: torch.Tensor) -> torch.Tensor:
     """fp32 K-major weights -> the storage FTC_FLAG_SPLIT16 expects: every 16-byte chunk of four fp32 values becomes
-    [hi x4 | lo x4] IEEE halves (hi = fp16(x), lo = fp16(x - hi)); same byte size, returned as a flat uint8 tensor."""
+    [hi x4 | lo x4] IEEE halves (xs = clamp(x, +-65504), hi = fp16(xs), lo = fp16(xs - hi): tests/x3_model.py split_hl); same byte size, returned as a flat uint8 tensor."""
     f = w.contiguous().float().reshape(-1, 4)
-    hi = f.clamp(-65504.0, 65504.0).to(torch.float16)
+    f = f.clamp(-65504.0, 65504.0)
+    hi = f.to(torch.float16)
     lo = (f - hi.float()).to(torch.float16)
     return torch.cat([hi, lo], dim=1).contiguous().view(torch.uint8).reshape(-1)
 
