@@ -344,6 +344,9 @@ __global__ __launch_bounds__(256) void dwconv_strip_kernel(const T* __restrict__
 //           hidden unit as a float4 dot product + wave64 shuffle reduction.
 //   se_fc2: grid (ceil(C/256), B): one lane per output channel, fc2 stored transposed [S][C]
 //           so the S loads of a lane are coalesced across the wave and independent of each other.
+// Hidden vector, gates and folded weights of all five kernels (se_fc1, se_fc2<FOLD>, se_fc2_fold64, se_fc2_foldx3, the HPART
+// loader) are pinned bit for bit by tests/test_gpu_exact_mbconv.py::test_se_saturated: inputs on which every sum is exact and
+// both activations sit in an exact regime (hidden = its pre-activation or -0, gate in {0, 0.5, 1}).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(512) void se_fc1_kernel(const float* __restrict__ partial, const float* __restrict__ w1,
                                                      const float* __restrict__ b1, float* __restrict__ hidden,

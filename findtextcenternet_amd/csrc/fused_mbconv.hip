@@ -23,6 +23,8 @@
 //
 // Numerics: identical rounding points AND K order to conv3x3 (+SiLU, 16-bit store) followed by conv1x1 (fp32 accumulate, + bias, + fp32 residual):
 // measured bit-identical to the two-launch form in its default tile configurations (tests/test_gpu_ops.py::test_fused_mbconv_block_in_one_launch).
+// Both forms are held bit for bit to one staged float64 model (e = r16(SiLU(.)), out in fp32, out2 = r16(out) | its pre-split copy) on the saturated-SiLU
+// operands of tests/exact_operands.py: tests/test_gpu_exact_mbconv.py::test_fmbconv_saturated.
 #include "conv_igemm_impl.h"
 #include "ftc_host.h"
 

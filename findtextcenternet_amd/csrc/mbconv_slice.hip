@@ -26,6 +26,9 @@
 // version of this kernel (64 channels, 256 threads, two workgroups per CU) moved 655 KB per 64 channels and took 54 us per stage-6
 // block -- its K loop ran at the 38 B/clk/CU the L2 delivered; 128 channels halve that traffic and balance it against the MFMA time
 // (per K step of 32: 45 KB of DMA against 36 MFMAs per SIMD).  Image b's workgroups are placed on XCD b % 8.
+// The rounding points above (e narrowed to the 16-bit type after its SiLU, depthwise and second SiLU in fp32, channel sums over the fp32 values before
+// the output is narrowed) are pinned bit for bit by tests/test_gpu_exact_mbconv.py on the saturated-SiLU operands of tests/exact_operands.py; hpart,
+// whose value depends on the order of its sum, is held to an a-priori bound there.
 #include "conv_igemm_impl.h"
 
 namespace {

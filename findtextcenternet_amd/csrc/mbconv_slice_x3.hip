@@ -18,6 +18,7 @@
 //   * 128-byte rows: chunk slot s of row r holds K chunk s ^ g(r), g(r) = ((r >> 1) & 7) ^ 2 (((r >> 2) ^ (r >> 3)) & 1) -- the 16-lane groups
 //     in which the LDS serves a ds_read_b128 ({0-3, 12-15, 20-27}, ..) find their 16 rows x {chunk c, chunk c ^ 2} in 16 different bank quads.
 // Activations: expf SiLU (the fp32 plans' epilogues), depthwise in fp32 FMA as dwconv_strip_kernel<float>.
+// e and d are never narrowed; tests/test_gpu_exact_mbconv.py pins out, the channel sums and the FTC_FLAG_PRESPLIT copy bit for bit on saturated-SiLU operands.
 #include "conv_igemm_impl.h"
 
 namespace {

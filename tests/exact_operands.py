@@ -15,6 +15,10 @@ the operands themselves instead of trusting the caller.
 
 This module holds no tests and launches nothing: the builders below return operands plus the float64 reference, the -m gpu modules
 run them, tests/test_exact_operands_host.py checks every case on the CPU.
+
+The kernels with a SiLU between two linear stages (MBHEAD, SE, FMBCONV, activated DWCONV / STEM) have families of their own at the end of
+the module ("saturated SiLU"): every pre-activation sits in a regime where the activation is exact, a staged float64 model gives the bits;
+run by tests/test_gpu_exact_mbconv.py, proved on the CPU by tests/test_exact_saturation_host.py.
 """
 from __future__ import annotations
 
@@ -448,3 +452,342 @@ def two_part_table_case(case, i=0, j=0, **kw):
     c = two_part_case(B, H, W, Cin, CinT, cin_off, Cout, k, stride, residual=residual, se=se, seed=zlib.crc32((name + "two-part").encode()) % 100000, i=i, j=j, **kw)
     c.CoutT, c.cout_off, c.name, c.mname = CoutT, cout_off, name, "f32x3"
     return c
+
+
+# ---- saturated SiLU: exact cases through the kernels with an activation between two linear stages -----------------------------------
+# Every SiLU in the tree is x / (1 + exp(-x)) or x * rcp(1 + exp2(-x log2 e)) (csrc/ftc_common.h), the SE gate is 1 / (1 + expf(-x)).
+# In fp32 these have exact regimes:
+#   pass    t >= 18     SiLU = t bit for bit: exp(-t) <= 2^-24 from t >= 16.64, so 1 + e rounds to 1 (and rcp(1) = 1); the float64 value
+#                       t (1 - 1.5e-8) rounds to t as well.  The gate is 1.
+#   block   t <= -120   SiLU = -0: exp overflows to +inf beyond 88.73, t / inf = t * rcp(inf) = -0; the true value is below 2^-150 from
+#                       t <= -110 and rounds to -0 too.  The gate is 0.
+#   zero    t = 0       SiLU = 0 / 2 = 0; the gate is exactly 0.5.
+# A large exact bias per channel puts every pre-activation of a case into one of them; the fused chain is then piecewise linear with known
+# rounding points, and a staged float64 model (round_out at the points the kernel headers document) predicts every output bit.
+# Channels: per 32-channel group a quarter is blocked at the first SiLU and another quarter at the second, interleaved with the passing
+# ones, the pattern rotating from group to group; pass biases differ between neighbouring channels.
+PASS_MIN = 18.0
+BLOCK_MAX = -120.0
+
+
+def _regimes(t):
+    t = t.double()
+    p, b, z = t >= PASS_MIN, t <= BLOCK_MAX, t == 0
+    n = int((~(p | b | z)).sum())
+    assert n == 0, f"{n} of {t.numel()} pre-activations are in no exact regime (e.g. {float(t[~(p | b | z)][0])!r})"
+    return t, p, b
+
+
+def silu_sat64(t):
+    """SiLU of pre-activations that are ALL in an exact regime (asserted): t | -0 | 0, in float64."""
+    t, p, b = _regimes(t)
+    return torch.where(p, t, torch.where(b, torch.full_like(t, -0.0), torch.zeros_like(t)))
+
+
+def gate_sat64(t):
+    """Sigmoid of pre-activations that are ALL in an exact regime (asserted): 1 | 0 | 0.5."""
+    t, p, b = _regimes(t)
+    return torch.where(p, torch.ones_like(t), torch.where(b, torch.zeros_like(t), torch.full_like(t, 0.5)))
+
+
+def sat_channels(C, which):
+    """Bool [C]: the channels blocked at SiLU number `which` (0 | 1): one residue of (c + c // 32) mod 4 each."""
+    c = torch.arange(C)
+    return (c + c // 32) % 4 == (1 if which == 0 else 3)
+
+
+def sat_bias(C, blocked, base, block, mul):
+    """base + a 3-bit code that differs between neighbours (and between c and c + 8) on passing channels, `block` on blocked ones."""
+    c = torch.arange(C)
+    return torch.where(blocked, torch.full((C,), float(block)), base + ((c * mul + c // 8) % 8).float())
+
+
+def assert_channel_mix(blocked_list, C, slice_w):
+    """Per slice: at least a quarter of the channels blocked at each SiLU, at least half passing each; both kinds in every 32-channel group."""
+    for blk in blocked_list:
+        for c0 in range(0, C, slice_w):
+            n = int(blk[c0:c0 + slice_w].sum())
+            assert 4 * n >= slice_w and 2 * (slice_w - n) >= slice_w, (c0, n, slice_w)
+        for c0 in range(0, C, 32):
+            g_ = blk[c0:c0 + 32]
+            assert bool(g_.any()) and bool((~g_).any())
+            assert bool((g_[1:] != g_[:-1]).any())
+
+
+def assert_terms_exact(terms, dim, addends=(), what=""):
+    """terms: the exact float64 terms of a sum along `dim`; addends: what is added to the sum.  With 2^-s their common grid,
+    (sum |terms| + sum |addends|) 2^s < 2^24 for every output: each partial sum in any order is an fp32 value.  Returns the largest such figure."""
+    s = max([grid(terms)] + [grid(a) for a in addends])
+    tot = terms.abs().sum(dim)
+    for a in addends:
+        tot = tot + a.abs().double()
+    units = float(tot.max()) * 2.0 ** s
+    assert units < 2.0 ** 24, f"{what}: sum |terms| reaches {units:.3e} units of 2^-{s}"
+    return units
+
+
+def any_order_bound(terms, dim, n):
+    """A-priori bound of an fp32 sum of n terms in any order, each term carrying up to three roundings of its own: (n + 2) 2^-24 sum |terms|."""
+    return (n + 2) * 2.0 ** -24 * terms.abs().sum(dim)
+
+
+def depthwise_taps64(e, wd, bd, stride=1, drop=None):
+    """NHWC float64 depthwise 3x3 (pad 1) written tap by tap; drop = (mask [Ho, Wo] bool, r, c) leaves tap (r, c) out at the masked outputs."""
+    B, H, W, C = e.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    ep = F.pad(e.double(), (0, 0, 1, 1, 1, 1))
+    d = bd.double().expand(B, Ho, Wo, C).clone()
+    for r in range(3):
+        for c in range(3):
+            term = ep[:, r:r + stride * (Ho - 1) + 1:stride, c:c + stride * (Wo - 1) + 1:stride] * wd[:, 0, r, c].double()
+            if drop is not None and drop[1] == r and drop[2] == c:
+                term = term * (~drop[0])[None, :, :, None].double()
+            d = d + term
+    return d
+
+
+def border_masks(H, W):
+    """name -> [H, W] bool: the four borders and the interior."""
+    y, x = torch.arange(H)[:, None].expand(H, W), torch.arange(W)[None, :].expand(H, W)
+    m = {"top": y == 0, "bottom": y == H - 1, "left": x == 0, "right": x == W - 1}
+    m["interior"] = ~(m["top"] | m["bottom"] | m["left"] | m["right"])
+    return m
+
+
+def mbhead_model64(c, x=None, we=None, wd=None, round_e=True, sums_after_narrow=False, drop=None, px=None):
+    """Staged model of FTC_OP_MBHEAD (csrc/mbconv_slice.hip, mbconv_slice_x3.hip): t = expand + bias (fp32 accumulators); e = r16(SiLU(t)) (fp32
+    in the fp16x3 form); d = depthwise + bias in fp32; out = r16(SiLU(d)); channel sums per band over the fp32 SiLU(d) BEFORE narrowing;
+    hpart[b][band][slice][s] = sum over the slice of w1 * sums / (H W).  The keyword arguments are the mutations the host test applies."""
+    x = c.x if x is None else x
+    we = c.we if we is None else we
+    wd = c.wd if wd is None else wd
+    r16 = (lambda v: v) if c.x3 else (lambda v: round_out(v, c.dt).double())
+    if getattr(c, "two_part", False):              # the fp16x3 product of two-part operands: a_hi w_lo + a_lo w_hi + a_hi w_hi, the lo.lo term dropped by the spec
+        import x3_model as M
+        t = M.x3_ref64(x, we.reshape(c.C, c.K, 1, 1)) + c.be.double()
+    else:
+        t = torch.einsum("bhwk,ck->bhwc", x.double(), we.double()) + c.be.double()
+    a = silu_sat64(t)
+    e = r16(a) if round_e else a
+    d = depthwise_taps64(e, wd, c.bd, 1, drop)
+    act = silu_sat64(d)
+    out = act.float() if c.x3 else round_out(act, c.dt)
+    src = out.double() if sums_after_narrow else act
+    R = c.R if c.R else c.H
+    sums = torch.stack([src[:, j * R:(j + 1) * R].sum((1, 2)) for j in range(c.NB)], 1)             # [B, NB, C]
+    npx = R * c.W
+    sums_bound = (npx + 2) * 2.0 ** -24 * torch.stack([src[:, j * R:(j + 1) * R].abs().sum((1, 2)) for j in range(c.NB)], 1)
+    terms = (sums / float(px or c.H * c.W)).reshape(c.B, c.NB, c.NS, 1, c.slice_w) * c.w1.double().reshape(1, 1, c.S, c.NS, c.slice_w).permute(0, 1, 3, 2, 4)
+    # hpart: slice_w terms, each mean with two roundings of its own -- plus, where the sums themselves are only bounded, their npx + 2
+    n_hp = c.slice_w + (npx + 2 if getattr(c, "two_part", False) else 0)
+    return SimpleNamespace(t=t, e=e, d=d, act=act, out=out, sums=sums, sums_bound=sums_bound, hp=terms.sum(-1), hp_bound=any_order_bound(terms, -1, n_hp))
+
+
+def mbhead_sat_case(B, H, W, K, C, S, R, dt, slice_w, seed=0, x3=False, e_extra=0, two_part=False):
+    """FTC_OP_MBHEAD with both SiLUs saturated; x3: the fp16x3 form on one-part operands (the lo half of every split is zero).
+    Bitwise: out, the channel sums (per band).  Bounded (any_order_bound): hpart -- the means carry about 23 bits (and 1 / (H W) rounds
+    unless H W is a power of two), so fc1 * mean is not order-free.
+    two_part (fp16x3 only): operands whose lo half is never zero (acts2 / weights2).  The three-term product lies on the grid 2^-(11+s); with K = 32
+    (s = 2), depthwise weights in {0, +-1} and biases 640.. / -768, sum |terms| + |bias| of the depthwise stage stays below 2^24 units (2048): t, e, d and
+    out are fp32 values whatever the order, compared bitwise.  The channel sums are not (hundreds of 24-bit addends): they are held to
+    any_order_bound over the pixels of a band, and hpart to the bound of both sums together.
+    Proved here: the expand GEMM and the depthwise sum are order-free in fp32 (assert_exact_case), every pre-activation is in a regime
+    (silu_sat64 asserts), the channel mix, and that the sums of one sign stay below 2^24 units of their grid.
+    e_extra: the expand weights are 2^-e_extra finer.  fp16 holds t in [32, 64) to 2^-5, so on the default grid (2^-2 .. 2^-4) its rounding of e is
+    the identity; with e_extra = 4 it rounds, which the channel sums can afford only on maps (bands) of a few hundred pixels."""
+    g = gen(seed)
+    s = shift_for(K) + e_extra
+    NB = -(-H // R) if R else 1
+    assert not two_part or (x3 and K <= 64)
+    x = (acts2 if two_part else acts)((B, H, W, K), g)
+    we = (weights2 if two_part else weights)((C, K), s, g)
+    wd = torch.randint(-1, 2, (C, 1, 3, 3), generator=g).float() if two_part else weights((C, 1, 3, 3), 2, g)
+    blk_e, blk_d = sat_channels(C, 0), sat_channels(C, 1)
+    assert_channel_mix([blk_e, blk_d], C, slice_w)
+    be = sat_bias(C, blk_e, 40.0, -160.0, 3)
+    bd = sat_bias(C, blk_d, 640.0, -768.0, 5) if two_part else sat_bias(C, blk_d, 288.0, -512.0, 5)
+    w1 = weights((S, C), shift_for(slice_w), g)
+    c = SimpleNamespace(B=B, H=H, W=W, K=K, C=C, S=S, R=R, NB=NB, NS=C // slice_w, slice_w=slice_w, dt=dt, x3=x3, two_part=two_part, x=x, we=we, be=be, wd=wd, bd=bd, w1=w1,
+                        blk_e=blk_e, blk_d=blk_d)
+    if two_part:
+        import x3_model as M
+        M.assert_exact_x3(M.x3_terms(x, we.reshape(C, K, 1, 1)), 1, 0, [be])
+        m = mbhead_model64(c)
+        assert torch.equal(m.t.float().double(), m.t)
+        units = float(depthwise_taps64(m.e.abs(), wd.abs(), bd.abs()).max()) * 2.0 ** max(grid(m.e), grid(bd))
+        assert units < 2.0 ** 24, f"depthwise stage reaches {units:.3e} units"
+    else:
+        assert_exact_case([x, we], K, [be], [(x, L.F16 if x3 else dt), (we, L.F16 if x3 else dt)], L.F32)
+        m = mbhead_model64(c)
+        assert_exact_case([m.e, wd], 9, [bd], [(m.e, L.F32 if x3 else dt)], L.F32, m.d)
+    assert torch.equal(m.d.float().double(), m.d)
+    if not x3 and dt == L.F16:
+        assert float(m.act.abs().max()) < 65504.0
+    c.sum_units = None if two_part else max(assert_terms_exact(m.act[:, j * (R or H):(j + 1) * (R or H)], (1, 2), what="channel sums") for j in range(NB))
+    c.m = m
+    return c
+
+
+def dwconv_silu_sat_case(B, H, W, C, stride, dt, seed=0):
+    """FTC_OP_DWCONV with ACT_SILU saturated: output and the partial channel sums (fp32, before narrowing) bitwise."""
+    g = gen(seed)
+    x = acts((B, H, W, C), g)
+    w = weights((C, 1, 3, 3), 5, g)                        # d = 160 + code +- 1.7 on the grid 2^-5: bf16 (step 1) and fp16 (step 2^-3) both round
+    blk = sat_channels(C, 0)
+    bias = sat_bias(C, blk, 160.0, -160.0, 3)
+    c = SimpleNamespace(B=B, H=H, W=W, C=C, stride=stride, dt=dt, x=x, w=w, bias=bias, blk=blk)
+    c.m = dwconv_model64(c)
+    assert_exact_case([x, w], 9, [bias], [(x, dt)], dt, c.m.d)
+    assert_terms_exact(c.m.act, (1, 2), what="dwconv channel sums")
+    return c
+
+
+def dwconv_model64(c, w=None, drop=None, sums_after_narrow=False):
+    d = depthwise_taps64(c.x, c.w if w is None else w, c.bias, c.stride, drop)
+    act = silu_sat64(d)
+    out = round_out(act, c.dt)
+    return SimpleNamespace(d=d, act=act, out=out, sums=(out.double() if sums_after_narrow else act).sum((1, 2)), Ho=d.shape[1], Wo=d.shape[2])
+
+
+def stem_silu_sat_case(B, H, W, C0, odt, seed=0):
+    """FTC_OP_STEM (3x3 stride 2 on 2 * image - 1, image in {0, 0.5, 1}) with ACT_SILU saturated."""
+    g = gen(seed)
+    img = stem_images((B, H, W, 3), g)
+    w = weights((C0, 3, 3, 3), 5, g)                       # as dwconv_silu_sat_case: both 16-bit types round the output
+    blk = (torch.arange(C0) % 4) == 1
+    bias = sat_bias(C0, blk, 160.0, -160.0, 3)
+    c = SimpleNamespace(B=B, H=H, W=W, C0=C0, odt=odt, img=img, w=w, bias=bias, blk=blk)
+    c.m = stem_model64(c)
+    assert_exact_case([img * 2 - 1, w], 27, [bias], [], odt, c.m.z)
+    return c
+
+
+def stem_model64(c, w=None):
+    z = conv_ref64(c.img * 2 - 1, c.w if w is None else w, 2, 1) + c.bias.double()
+    act = silu_sat64(z)
+    return SimpleNamespace(z=z, act=act, out=round_out(act, c.odt))
+
+
+def se_sat_case(B, C, S, P, HW, N, dt, hpart, seed=0, x3=False, flip=None):
+    """FTC_OP_SE on exact synthetic inputs, both activations saturated.  hpart False: P partial channel sums [B, P, C] (small integers; HW a power of
+    two, so the means are exact) through fc1; True: P per-slice partial products [B, P, S] handed over as FTC_OP_MBHEAD would.  The hidden
+    pre-activation of unit s in image b is 32 (pass) or -160 (block) plus a few units, by a per-image code: carried on channel s of the means
+    (w1[s, s] = 4, the rest of the S x S block zero) or on slice 0 of the partial products.  fc2 carries +-16 on unit c mod S and 2^-6 elsewhere: a passing
+    unit decides the gate of its channels, a blocked one leaves it to b2 = +-192; every third channel has a zero fc2 row and b2 = 0: gate 0.5.
+    flip = (b, s): that unit's code inverted, everything else as drawn (the one-entry perturbation).
+    Bitwise: hidden (plain form), scale, folded weights (N rows of {+-1, +-2} 2^-s times a gate in {0, 0.5, 1}: exact)."""
+    assert HW & (HW - 1) == 0
+    g = gen(seed)
+    code = torch.randint(0, 2, (B, S), generator=g).bool()
+    code[:, 0], code[:, 1 % S] = True, torch.arange(B) % 2 == 0            # every image passes unit 0; unit 1 alternates: no two neighbouring images alike
+    if flip is not None:
+        code[flip] = ~code[flip]
+    b1 = small_ints((S,), 0, g)
+    if hpart:
+        hp = small_ints((B, P, S), 2, g)
+        hp[:, 0] += torch.where(code, 32.0, -160.0)
+        a = hp.double().sum(1)
+        assert_terms_exact(hp.double(), 1, [b1], "hidden from partial products")
+        part = w1 = None
+    else:
+        assert C >= S
+        part = torch.randint(-3, 4, (B, P, C), generator=g).float() * max(1, HW // 4)                  # the means are multiples of 1/4
+        part[:, :, :S] = 0
+        part[:, 0, :S] = torch.where(code, 8.0, -40.0) * HW
+        w1 = weights((S, C), shift_for(C), g)
+        w1[:, :S] = torch.eye(S) * 4.0
+        mean = part.double().sum(1) / HW
+        assert_terms_exact(part.double(), 1, what="partial sums")
+        assert torch.equal(mean.float().double(), mean)
+        a = mean @ w1.double().t()
+        assert_terms_exact(mean[:, None, :] * w1.double()[None], 2, [b1], "fc1")
+        hp = None
+    hid = silu_sat64(a + b1.double())
+    cidx = torch.arange(C)
+    half = cidx % 3 == 2
+    w2 = weights((C, S), 6, g)
+    w2[cidx, cidx % S] = torch.where(cidx % 2 == 0, 16.0, -16.0)
+    w2[half] = 0
+    b2 = torch.where(half, torch.zeros(C), torch.where((cidx // 2) % 2 == 0, torch.full((C,), 192.0), torch.full((C,), -192.0)))
+    acc = hid @ w2.double().t() + b2.double()
+    assert_terms_exact(hid[:, None, :] * w2.double()[None], 2, [b2], "fc2")
+    gate = gate_sat64(acc)
+    for b in range(B):
+        assert {0.0, 0.5, 1.0} <= set(gate[b].unique().tolist()), "an image lacks a gate value"
+        assert b == 0 or not torch.equal(gate[b], gate[b - 1])
+    wp = weights((N, C), shift_for(C), g)
+    wb = wp.double()[None] * gate[:, None, :]
+    want_wb = wb.float() if x3 else round_out(wb, dt)
+    return SimpleNamespace(B=B, C=C, S=S, P=P, HW=HW, N=N, dt=dt, x3=x3, part=part, hp=hp, w1=w1, b1=b1, w2=w2, b2=b2, wp=wp, code=code,
+                           hid=hid.float(), gate=gate.float(), wb=want_wb)
+
+
+def fmbconv_model64(c, x=None, w1=None, w2=None, round_e=True, drop=None):
+    """Staged model of FTC_OP_FMBCONV (csrc/fused_mbconv.hip) and of its two-launch form: e = r16(SiLU(conv3x3 + b1)) (fp32 in the fp16x3 form);
+    out = fp32 project + b2 (+ residual); out2 = r16(out) (the pre-split copy of out in the fp16x3 form).  drop = (mask [H, W], r, k): tap (r, k) of
+    the 3x3 left out at the masked pixels."""
+    x = (c.x if x is None else x).double()
+    w1 = (c.w1 if w1 is None else w1).double()
+    w2 = c.w2 if w2 is None else w2
+    xp = F.pad(x, (0, 0, 1, 1, 1, 1))
+    t = c.b1.double().expand(c.B, c.H, c.W, c.E).clone()
+    for r in range(3):
+        for k in range(3):
+            term = torch.einsum("bhwi,ei->bhwe", xp[:, r:r + c.H, k:k + c.W], w1[:, :, r, k])
+            if drop is not None and drop[1] == r and drop[2] == k:
+                term = term * (~drop[0])[None, :, :, None].double()
+            t = t + term
+    a = silu_sat64(t)
+    e = a if (c.x3 or not round_e) else round_out(a, c.dt).double()
+    z = torch.einsum("bhwe,oe->bhwo", e, w2.double()) + c.b2.double()
+    if c.res is not None:
+        z = z + c.res.double()
+    return SimpleNamespace(t=t, e=e, z=z, out=round_out(z, L.F32), out2=None if c.x3 else round_out(z, c.dt))
+
+
+def fmbconv_sat_case(B, H, W, Cin, E, Cout, residual, dt, seed=0, x3=False):
+    """FTC_OP_FMBCONV with its SiLU saturated: out and out2 bitwise.  A quarter of the E expanded channels is blocked (interleaved, per 32-channel
+    group); fp16 gets expand weights four times finer, so that its rounding of e (2^-5 in [32, 64)) is not the identity."""
+    g = gen(seed)
+    K = 9 * Cin
+    s1 = shift_for(K) + (2 if (dt == L.F16 and not x3) else 0)
+    x = acts((B, H, W, Cin), g)
+    w1 = weights((E, Cin, 3, 3), s1, g)
+    blk = sat_channels(E, 0)
+    assert_channel_mix([blk], E, 128)
+    b1 = sat_bias(E, blk, 40.0, -160.0, 3)
+    s2 = shift_for(E)
+    w2 = weights((Cout, E), s2, g)
+    b2 = small_ints((Cout,), s2, g)
+    res = small_ints((B, H, W, Cout), s2, g) if residual else None
+    c = SimpleNamespace(B=B, H=H, W=W, Cin=Cin, E=E, Cout=Cout, dt=dt, x3=x3, x=x, w1=w1, b1=b1, w2=w2, b2=b2, res=res, blk=blk)
+    cdt = L.F16 if x3 else dt
+    assert_exact_case([x, w1], K, [b1], [(x, cdt), (w1, cdt), (w2, cdt)], L.F32)
+    c.m = m = fmbconv_model64(c)
+    assert_exact_case([m.e, w2], E, [b2] + ([res] if residual else []), [(m.e, L.F32 if x3 else dt)], L.F32 if x3 else dt, m.z)
+    return c
+
+
+def mbconv_tail_sat_case(dt, x3=False, seed=0):
+    """The MBConv tail end to end: FTC_OP_MBHEAD -> FTC_OP_SE (fold) -> project FTC_OP_CONV with per-image weights and residual.  The head is a
+    mbhead_sat_case (8x8 map, two slices), the SE inputs are a se_sat_case handed over as partial products (so the gates are exact and the chain
+    does not inherit the rounding of hpart), the project output y = sum_c out[b, p, c] * r16(wp[n, c] * gate[b, c]) + bias + residual is proved
+    order-free from its exact terms.  In the fp16x3 form `out` carries 15 bits: the project convolution splits it into two non-zero halves, each
+    product with the one-part folded weight is still exact."""
+    slice_w = 64 if x3 else 128 if dt == L.BF16 else 96
+    B, H, W, K, S, N = 2, 8, 8, 32, 7, 64
+    C = 2 * slice_w
+    head = mbhead_sat_case(B, H, W, K, C, S, 0, dt, slice_w, seed=seed, x3=x3)
+    se = se_sat_case(B, C, S, 2, H * W, N, dt, True, seed=seed + 1, x3=x3)
+    g = gen(seed + 2)
+    s = grid(se.wp)
+    bp, res = small_ints((N,), s, g), small_ints((B, H, W, N), s, g)
+    out = head.m.out.double()
+    terms = out.reshape(B, H * W, 1, C) * se.wb.double().reshape(B, 1, N, C)
+    y = terms.sum(-1).reshape(B, H, W, N) + bp.double() + res.double()
+    assert_terms_exact(terms.reshape(B, H, W, N, C), 4, [bp.expand(B, H, W, N), res], "project")
+    if not x3:
+        assert torch.equal(round_out(out * se.gate.double()[:, None, None, :], dt).double(), out * se.gate.double()[:, None, None, :])   # the FTC_FLAG_SE_SCALE route gates the activation
+    else:
+        assert float(out.abs().max()) < 65504.0 and grid(out) <= 21
+    return SimpleNamespace(head=head, se=se, bp=bp, res=res, N=N, y=round_out(y, L.F32), dt=dt, x3=x3)
