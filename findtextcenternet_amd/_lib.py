@@ -55,6 +55,12 @@ OCR_EXPORTS = ["ftc_ocr_abi_version", "ftc_ocr_assemble"]
 FTC_PREP_ABI_VERSION = 1
 PREP_EXPORTS = ["ftc_prep_abi_version", "ftc_page_ink", "ftc_page_fill_scratch_bytes", "ftc_page_fill", "ftc_features_at"]
 
+# include/ftc_sample.h (training-sample synthesis: the reference's dataset/processer.pyx as one batched device call)
+FTC_SAMPLE_ABI_VERSION = 1
+SAMPLE_NEAREST, SAMPLE_BLANK, SAMPLE_COLOUR = 1, 2, 4
+SAMPLE_MONO, SAMPLE_SINGLE, SAMPLE_DOUBLE, SAMPLE_BACKGROUND = range(4)
+SAMPLE_EXPORTS = ["ftc_sample_abi_version", "ftc_sample_synth"]
+
 
 class FtcLibraryError(RuntimeError):
     pass
@@ -104,6 +110,15 @@ class TextDims(C.Structure):
 
 class Tile(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("offset_x", "offset_y", "page_w", "page_h", "x_min", "x_max", "y_min", "y_max")]
+
+
+class SampleDesc(C.Structure):
+    """ftc_sample_desc of include/ftc_sample.h: 280 bytes, no padding."""
+    _fields_ = [(n, C.c_void_p) for n in ("image", "textline", "sepline", "position", "codes", "bg_image")] + [
+        (n, C.c_int32) for n in ("im_h", "im_w", "map_h", "map_w", "n_glyphs", "flags", "compose", "reserved", "inv_y0", "inv_x0", "inv_y1", "inv_x1",
+                                 "dbl_top", "dbl_bottom", "dbl_left", "dbl_right", "bg_h", "bg_w", "bg_y0", "bg_x0")] + [
+        ("fwd", C.c_float * 9), ("inv", C.c_float * 9), ("inv2", C.c_float * 9), ("startx", C.c_float), ("starty", C.c_float),
+        ("fg1", C.c_float * 3), ("fg2", C.c_float * 3), ("bg", C.c_float * 3)]
 
 
 _lib = None
@@ -209,6 +224,10 @@ def load():
     lib.ftc_page_fill_scratch_bytes.restype = i64
     lib.ftc_page_fill.argtypes = [vp, vp, i32, vp, vp, vp, C.c_float, C.c_double, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]
     lib.ftc_features_at.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp]
+    lib.ftc_sample_abi_version.restype = i32
+    lib.ftc_sample_synth.argtypes = [C.POINTER(SampleDesc), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    if lib.ftc_sample_abi_version() != FTC_SAMPLE_ABI_VERSION:
+        raise FtcLibraryError(f"sample ABI mismatch: library {lib.ftc_sample_abi_version()} vs binding {FTC_SAMPLE_ABI_VERSION}")
     if lib.ftc_prep_abi_version() != FTC_PREP_ABI_VERSION:
         raise FtcLibraryError(f"prep ABI mismatch: library {lib.ftc_prep_abi_version()} vs binding {FTC_PREP_ABI_VERSION}")
     if lib.ftc_ocr_abi_version() != FTC_OCR_ABI_VERSION:

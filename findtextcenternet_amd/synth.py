@@ -85,7 +85,10 @@ def adamw_case(ci: int):
 
 # ---- training / validation labels (config 5: train1.py data layout) --------------------------------------------------------
 def train_labels(seed: int, b: int, h: int, w: int, n_glyphs: int = 0):
-    """Synthetic label maps with the semantics of the reference's sample synthesiser (dataset/processer.pyx:133-202):
+    """Synthetic label maps that LOOK like the reference's training labels (dataset/processer.pyx:133-202) but are not its synthesis: a
+    cheap seeded stand-in that feeds the benchmark, the goldens g7 / g9 / g10 and the training tests.  The reference's real sample
+    synthesis -- affine crop, Gaussian centre map, box and id maps, rasters, colouring, bit-for-bit -- is ``findtextcenternet_amd.sample.
+    SampleSynth`` (include/ftc_sample.h).  What this function makes:
 
     labelmap [B,5,h,w] f32 -- 0: Gaussian centre map (max of per-glyph kernels, exactly 1.0 at a glyph centre),
                               1-2: log-size maps ``log(px/1024)+3`` inside the glyph ellipse, 3: text-line map, 4: separator map (0..1);
