@@ -390,22 +390,66 @@ __global__ __launch_bounds__(512) void se_fc1_kernel(const float* __restrict__ p
 
 // Hidden vector of the SE MLP into LDS: what se_fc1_kernel stored, or (FTC_FLAG_SE_HPART) SiLU(b1 + the C/64 per-slice partial products
 // FTC_OP_MBHEAD wrote, added in slice order: deterministic) -- the fc1 launch and its re-read of the channel sums disappear.
+// A lane requests its bias and SE_HCHUNK partial products (NS is 30 and 32 in the batch-8 plans, 60 in stage 5: one batch, two there)
+// before it adds the first one: one memory round trip per batch, not one per four.  The sum keeps its association: four partial sums
+// over j = 0..3 (mod 4) in increasing j for j < 4 * (NS / 4), the remainder onto the first, then ((a0 + a1) + (a2 + a3)) + b1
+// (SE_HCHUNK is a multiple of 4).  Past the end a batch re-reads row NS - 1 (no branch between the loads) and leaves the value unused.
+constexpr int SE_HCHUNK = 32;
+__device__ __forceinline__ float se_hpart_sum(const float* __restrict__ hp, int S, int NS, int s) {
+    static_assert(SE_HCHUNK % 4 == 0, "whole groups of four");
+    // buffer loads: the row offset in a scalar register + one lane offset, no address pair per load (a batch spans < 2^31 bytes: S <= 16000)
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (int j0 = 0; j0 < NS; j0 += SE_HCHUNK) {
+        const int nb = min(NS - j0, SE_HCHUNK);                    // rows of this batch
+        const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hp + (long)j0 * S), 0, nb * S * 4, 0x00020000);
+        float v[SE_HCHUNK];
+        int row_off = 0;                                           // bytes; stops at the batch's last row
+#pragma unroll
+        for (int e = 0; e < SE_HCHUNK; ++e) {
+            v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, s * 4, row_off, 0));
+            row_off = e + 1 < nb ? row_off + S * 4 : row_off;
+            asm volatile("" : "+s"(row_off));                      // one running scalar, not SE_HCHUNK of them computed ahead
+        }
+#pragma unroll
+        for (int e = 0; e < SE_HCHUNK; e += 4) {
+            const int j = j0 + e;
+            if (j + 4 <= NS) {
+                a0 += v[e];
+                a1 += v[e + 1];
+                a2 += v[e + 2];
+                a3 += v[e + 3];
+            } else {                                               // the remainder (j + 3 >= NS), in order onto a0
+                if (j < NS) a0 += v[e];
+                if (j + 1 < NS) a0 += v[e + 1];
+                if (j + 2 < NS) a0 += v[e + 2];
+            }
+        }
+    }
+    return (a0 + a1) + (a2 + a3);
+}
+// Hidden units past the first `nthreads` (S > 256: not in this network): the same sum, four loads at a time.
+__device__ __forceinline__ float se_hpart_sum_serial(const float* __restrict__ hp, int S, int NS, int s) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    int j = 0;
+    for (; j + 4 <= NS; j += 4) {
+        a0 += hp[(long)j * S + s];
+        a1 += hp[(long)(j + 1) * S + s];
+        a2 += hp[(long)(j + 2) * S + s];
+        a3 += hp[(long)(j + 3) * S + s];
+    }
+    for (; j < NS; ++j) a0 += hp[(long)j * S + s];
+    return (a0 + a1) + (a2 + a3);
+}
 __device__ __forceinline__ void se_load_hidden(float* hid, const float* __restrict__ hidden, const float* __restrict__ hpart,
                                                const float* __restrict__ b1, int b, int S, int NS, int t, int nthreads) {
     if (hpart) {
         const float* hp = hpart + (long)b * NS * S;
-        for (int s = t; s < S; s += nthreads) {
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-            int j = 0;
-            for (; j + 4 <= NS; j += 4) {                      // four independent loads in flight; the association is fixed
-                a0 += hp[(long)j * S + s];
-                a1 += hp[(long)(j + 1) * S + s];
-                a2 += hp[(long)(j + 2) * S + s];
-                a3 += hp[(long)(j + 3) * S + s];
-            }
-            for (; j < NS; ++j) a0 += hp[(long)j * S + s];
-            hid[s] = act_silu_precise(((a0 + a1) + (a2 + a3)) + b1[s]);
+        if (t < S) {
+            const float bias = b1[t];
+            const float sum = se_hpart_sum(hp, S, NS, t);
+            hid[t] = act_silu_precise(sum + bias);
         }
+        for (int s = t + nthreads; s < S; s += nthreads) hid[s] = act_silu_precise(se_hpart_sum_serial(hp, S, NS, s) + b1[s]);
     } else {
         for (int s = t; s < S; s += nthreads) hid[s] = hidden[(long)b * S + s];
     }
@@ -462,12 +506,17 @@ __global__ __launch_bounds__(256) void se_fc2_kernel(const float* __restrict__ h
 // (all of a lane's S/4 loads independent and unrolled), the four partial dots meet in LDS in fixed order, and the 64 scale values
 // then stream the [N][64] column block of the project weights: 8 lanes x 16 B per row, 32 rows per pass, rows split over gridDim.z.
 // Same arithmetic per element as se_fc2_kernel<true> except for the association of the S-sum (4 partial sums of S/4 terms).
-template <typename T>
-__global__ __launch_bounds__(256) void se_fc2_fold64_kernel(const float* __restrict__ hidden, const float* __restrict__ w2t,
-                                                            const float* __restrict__ b2, float* __restrict__ scale, int C, int S,
-                                                            const T* __restrict__ wp, T* __restrict__ wb, int N,
-                                                            const float* __restrict__ hpart, const float* __restrict__ b1, int NS) {
-    extern __shared__ __attribute__((aligned(16))) float lds_f[];      // [S] hidden | [4][64] partial dots | [64] scale
+//
+// Dependent memory round trips, not bytes, bound these launches (~9 us even when the fold writes 2 MB).  The data need exactly one: the
+// hidden vector (or the partial products it is summed from) that the previous launch wrote.  So everything else is requested at kernel
+// entry, in one batch with it: the first SE_PF fold rows of this lane (they do not depend on the gates), b2, the lane's fc2 column
+// (S <= 160: at most 40 values), b1 and the partial products.  Between that batch's wait and the first store only the fold's next rows are requested (se_fold_rows).
+
+// Gates of the workgroup's 64 channels into lsc[0..64) (and scale[], z-slice 0); returns after the barrier that publishes them.
+// lds_f: [S] hidden | [4][64] partial dots | [64] scale.
+__device__ __forceinline__ const float* se_gates64(float* lds_f, const float* __restrict__ hidden, const float* __restrict__ w2t,
+                                                   const float* __restrict__ b2, float* __restrict__ scale, int C, int S,
+                                                   const float* __restrict__ hpart, const float* __restrict__ b1, int NS) {
     float* hid = lds_f;
     float* part = lds_f + ((S + 3) & ~3);
     float* lsc = part + 256;
@@ -475,48 +524,130 @@ __global__ __launch_bounds__(256) void se_fc2_fold64_kernel(const float* __restr
     const int cl = t & 63, sg = t >> 6;
     const int c = blockIdx.x * 64 + cl;
     const int s_lo = sg * ((S + 3) / 4), s_hi = min(S, s_lo + (S + 3) / 4);
-    // Dependent memory round trips, not bytes, bound this kernel (it takes ~9 us even when the fold writes 2 MB): the fc2 column of
-    // this lane does not depend on the hidden vector, so its S/4 loads are issued before the hidden vector is even requested
-    // (S <= 160: at most 40 per lane) and everything is in flight together.
+    const int cnt = __builtin_amdgcn_readfirstlane(s_hi - s_lo);      // the same for the whole wave (sg = t >> 6)
+    const float b2c = c < C ? b2[c] : 0.f;
     constexpr int SMAX = 40;
     float wreg[SMAX];
 #pragma unroll
-    for (int i = 0; i < SMAX; ++i) wreg[i] = (c < C && s_lo + i < s_hi) ? w2t[(long)(s_lo + i) * C + c] : 0.f;
+    for (int i = 0; i < SMAX; ++i) wreg[i] = (c < C && i < cnt) ? w2t[(long)(s_lo + i) * C + c] : 0.f;
     se_load_hidden(hid, hidden, hpart, b1, b, S, NS, t, 256);
+    // Every load of the batch has landed before the barrier (vmcnt(0); the waves that summed partial products have waited already, in
+    // order of issue): a wave without hidden units to load would otherwise meet its fc2 column's wait inside the dot product.
+    __builtin_amdgcn_s_waitcnt(0x0F70);
     __syncthreads();
+    // The wave's terms in order, as one chain of fused multiply-adds; the LDS reads of eight terms are issued together (the index is
+    // clamped, not predicated: a term past the wave's range reads a valid word and is not added).
+    int cnt_d = cnt;
+    asm volatile("" : "+s"(cnt_d));                                // a value of its own: else the 40 load predicates above are kept for here
     float acc = 0.f;
 #pragma unroll
-    for (int i = 0; i < SMAX; ++i)
-        if (s_lo + i < s_hi) acc += hid[s_lo + i] * wreg[i];
+    for (int i0 = 0; i0 < SMAX; i0 += 8) {
+        float h[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) h[e] = hid[min(s_lo + i0 + e, S - 1)];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc = i0 + e < cnt_d ? __builtin_fmaf(h[e], wreg[i0 + e], acc) : acc;
+    }
     for (int s = s_lo + SMAX; s < s_hi; ++s) acc += hid[s] * w2t[(long)s * C + c];      // (S > 160: not in this network)
     part[sg * 64 + cl] = acc;
     __syncthreads();
     if (t < 64) {
         float sc = 0.f;
         if (c < C) {
-            sc = sigmoid_precise(b2[c] + ((part[cl] + part[64 + cl]) + (part[128 + cl] + part[192 + cl])));
+            sc = sigmoid_precise(b2c + ((part[cl] + part[64 + cl]) + (part[128 + cl] + part[192 + cl])));
             if (blockIdx.z == 0) scale[(long)b * C + c] = sc;
         }
         lsc[cl] = sc;
     }
     __syncthreads();
+    return lsc;
+}
+
+constexpr int SE_PF = 2;                // fold rows a lane requests at kernel entry (they stay in registers through the whole prologue)
+constexpr int SE_FD = 8;                // fold rows a lane streams at a time afterwards (the prologue's registers are free by then)
+
+// 16 bytes of project weights -> 8 floats (what load16<T> returns for the same bytes)
+template <typename T> __device__ __forceinline__ void se_cvt16(u32x4 v, float (&f)[8]);
+template <> __device__ __forceinline__ void se_cvt16<__bf16>(u32x4 v, float (&f)[8]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f[2 * e] = __uint_as_float(v[e] << 16);
+        f[2 * e + 1] = __uint_as_float(v[e] & 0xffff0000u);
+    }
+}
+template <> __device__ __forceinline__ void se_cvt16<_Float16>(u32x4 v, float (&f)[8]) {
+    const f16x8 h = __builtin_bit_cast(f16x8, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = (float)h[e];
+}
+
+// Rows n, n + step, ... (R of them) below n_hi of a [N][rowq] matrix of 16-byte chunks, column `col`.
+template <int R>
+__device__ __forceinline__ void se_rows_load(u32x4 (&v)[R], const u32x4* __restrict__ wp, long rowq, int col, int n, int step, int n_hi, bool on) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const int nk = n + k * step;
+        v[k] = (on && nk < n_hi) ? wp[(long)nk * rowq + col] : u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
+// The fold of one lane: rows n0, n0 + step, ... below n_hi through store_row(n, chunk).  `pre` holds the first SE_PF rows; the others
+// stream SE_FD at a time, each batch requested before the one ahead of it is stored.  Inside the loop a batch is requested without a
+// branch (past the end it re-reads the lane's last row, unused): behind a branch the compiler cannot count the requests in flight and
+// waits for all of them, the batch just requested included, before the first store.
+template <typename F>
+__device__ __forceinline__ void se_fold_rows(const u32x4 (&pre)[SE_PF], const u32x4* __restrict__ wp, long rowq, int col, int n0, int step, int n_hi,
+                                             F store_row) {
+    u32x4 va[SE_FD], vb[SE_FD];                                   // two batches by turns: no register copies, which would wait for the newer one
+    int n = n0 + SE_PF * step;
+    if (n < n_hi) se_rows_load(va, wp, rowq, col, n, step, n_hi, true);
+#pragma unroll
+    for (int k = 0; k < SE_PF; ++k)
+        if (n0 + k * step < n_hi) store_row(n0 + k * step, pre[k]);
+    auto turn = [&](const u32x4 (&cur)[SE_FD], u32x4 (&nxt)[SE_FD]) {
+#pragma unroll
+        for (int k = 0; k < SE_FD; ++k) nxt[k] = wp[(long)min(n + (SE_FD + k) * step, n_hi - 1) * rowq + col];
+#pragma unroll
+        for (int k = 0; k < SE_FD; ++k)
+            if (n + k * step < n_hi) store_row(n + k * step, cur[k]);
+        n += SE_FD * step;
+    };
+    while (n < n_hi) {
+        turn(va, vb);
+        if (n >= n_hi) break;
+        turn(vb, va);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, 4) void se_fc2_fold64_kernel(const float* __restrict__ hidden, const float* __restrict__ w2t,
+                                                               const float* __restrict__ b2, float* __restrict__ scale, int C, int S,
+                                                               const T* __restrict__ wp, T* __restrict__ wb, int N,
+                                                               const float* __restrict__ hpart, const float* __restrict__ b1, int NS) {
+    extern __shared__ __attribute__((aligned(16))) float lds_f[];      // [S] hidden | [4][64] partial dots | [64] scale
+    const int b = blockIdx.y, t = threadIdx.x;
     const int chunk = t & 7, r0 = t >> 3;                         // 8 lanes x 8 channels = the 64-channel block, 32 rows per pass
     const int cc = blockIdx.x * 64 + chunk * 8;
-    if (cc >= C) return;                                           // C % 8 == 0 (validated)
+    const int rows = (N + gridDim.z - 1) / gridDim.z;
+    const int n_lo = blockIdx.z * rows, n_hi = min(N, n_lo + rows);
+    const u32x4* src = reinterpret_cast<const u32x4*>(wp);
+    const long rowq = C >> 3;                                      // C % 8 == 0 (validated)
+    const int col = cc >> 3;
+    u32x4 pre[SE_PF];
+    se_rows_load(pre, src, rowq, col, n_lo + r0, 32, n_hi, cc < C);
+    const float* lsc = se_gates64(lds_f, hidden, w2t, b2, scale, C, S, hpart, b1, NS);
+    if (cc >= C) return;
     float f[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] = lsc[chunk * 8 + e];
-    const int rows = (N + gridDim.z - 1) / gridDim.z;
-    const int n_lo = blockIdx.z * rows, n_hi = min(N, n_lo + rows);
-    T* dst = wb + (long)b * N * C;
-#pragma unroll 4
-    for (int n = n_lo + r0; n < n_hi; n += 32) {
+    T* dst = wb + (long)b * N * C + cc;
+    se_fold_rows(pre, src, rowq, col, n_lo + r0, 32, n_hi, [&](int n, u32x4 v) {
         float x[8];
-        load16<T>(wp + (long)n * C + cc, x);
+        se_cvt16<T>(v, x);
 #pragma unroll
         for (int e = 0; e < 8; ++e) x[e] *= f[e];
-        store16<T>(dst + (long)n * C + cc, x);
-    }
+        store16<T>(dst + (long)n * C, x);
+    });
 }
 
 // FOLD for the fp16x3 mode (FTC_FLAG_SPLIT16; the fp32 plan): the project weights are stored PRE-SPLIT -- every 16-byte chunk of four
@@ -524,52 +655,28 @@ __global__ __launch_bounds__(256) void se_fc2_fold64_kernel(const float* __restr
 // w * scale, clamped and split again (same split as conv_igemm_impl.h chunk_hl).  With it the project convolution of the fp16x3 plan streams both
 // operands by DMA like the 16-bit plans do, instead of gating every activation element while staging it (87 us per stage-6 block).
 // Same prologue as se_fc2_fold64_kernel (64 channels per workgroup); 16 lanes x one chunk = the 64 channels, 16 rows per pass.
-__global__ __launch_bounds__(256) void se_fc2_foldx3_kernel(const float* __restrict__ hidden, const float* __restrict__ w2t,
+// (round 5: FTC_FLAG_SE_HPART in the fp16x3 plan too -- the fused head's partial products)
+__global__ __launch_bounds__(256, 4) void se_fc2_foldx3_kernel(const float* __restrict__ hidden, const float* __restrict__ w2t,
                                                             const float* __restrict__ b2, float* __restrict__ scale, int C, int S,
                                                             const u32x4* __restrict__ wp, u32x4* __restrict__ wb, int N,
                                                             const float* __restrict__ hpart, const float* __restrict__ b1, int NS) {
     extern __shared__ __attribute__((aligned(16))) float lds_f[];      // [S] hidden | [4][64] partial dots | [64] scale
-    float* hid = lds_f;
-    float* part = lds_f + ((S + 3) & ~3);
-    float* lsc = part + 256;
     const int b = blockIdx.y, t = threadIdx.x;
-    const int cl = t & 63, sg = t >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    const int s_lo = sg * ((S + 3) / 4), s_hi = min(S, s_lo + (S + 3) / 4);
-    constexpr int SMAX = 40;
-    float wreg[SMAX];
-#pragma unroll
-    for (int i = 0; i < SMAX; ++i) wreg[i] = (c < C && s_lo + i < s_hi) ? w2t[(long)(s_lo + i) * C + c] : 0.f;
-    se_load_hidden(hid, hidden, hpart, b1, b, S, NS, t, 256);          // (round 5: FTC_FLAG_SE_HPART in the fp16x3 plan too -- the fused head's partial products)
-    __syncthreads();
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < SMAX; ++i)
-        if (s_lo + i < s_hi) acc += hid[s_lo + i] * wreg[i];
-    for (int s = s_lo + SMAX; s < s_hi; ++s) acc += hid[s] * w2t[(long)s * C + c];
-    part[sg * 64 + cl] = acc;
-    __syncthreads();
-    if (t < 64) {
-        float sc = 0.f;
-        if (c < C) {
-            sc = sigmoid_precise(b2[c] + ((part[cl] + part[64 + cl]) + (part[128 + cl] + part[192 + cl])));
-            if (blockIdx.z == 0) scale[(long)b * C + c] = sc;
-        }
-        lsc[cl] = sc;
-    }
-    __syncthreads();
     const int chunk = t & 15, r0 = t >> 4;
     const int cc = blockIdx.x * 64 + chunk * 4;
-    if (cc >= C) return;                                           // C % 4 == 0 (validated)
+    const int rows = (N + gridDim.z - 1) / gridDim.z;
+    const int n_lo = blockIdx.z * rows, n_hi = min(N, n_lo + rows);
+    const long rowq = C >> 2;                                      // C % 4 == 0 (validated)
+    const int col = cc >> 2;
+    u32x4 pre[SE_PF];
+    se_rows_load(pre, wp, rowq, col, n_lo + r0, 16, n_hi, cc < C);
+    const float* lsc = se_gates64(lds_f, hidden, w2t, b2, scale, C, S, hpart, b1, NS);
+    if (cc >= C) return;
     float f[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) f[e] = lsc[chunk * 4 + e];
-    const int rows = (N + gridDim.z - 1) / gridDim.z;
-    const int n_lo = blockIdx.z * rows, n_hi = min(N, n_lo + rows);
-    u32x4* dst = wb + (long)b * N * (C >> 2);
-#pragma unroll 4
-    for (int n = n_lo + r0; n < n_hi; n += 16) {
-        const u32x4 v = wp[(long)n * (C >> 2) + (cc >> 2)];
+    u32x4* dst = wb + (long)b * N * rowq + col;
+    se_fold_rows(pre, wp, rowq, col, n_lo + r0, 16, n_hi, [&](int n, u32x4 v) {
         typedef _Float16 h4 __attribute__((ext_vector_type(4)));
         const u32x2 hu = {v[0], v[1]}, lu = {v[2], v[3]};
         const h4 hi = __builtin_bit_cast(h4, hu), lo = __builtin_bit_cast(h4, lu);
@@ -582,8 +689,8 @@ __global__ __launch_bounds__(256) void se_fc2_foldx3_kernel(const float* __restr
             ol[e] = (_Float16)(x - (float)hh);
         }
         const u32x2 ohu = __builtin_bit_cast(u32x2, oh), olu = __builtin_bit_cast(u32x2, ol);
-        dst[(long)n * (C >> 2) + (cc >> 2)] = u32x4{ohu[0], ohu[1], olu[0], olu[1]};
-    }
+        dst[(long)n * rowq] = u32x4{ohu[0], ohu[1], olu[0], olu[1]};
+    });
 }
 
 }  // namespace
