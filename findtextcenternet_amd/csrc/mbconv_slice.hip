@@ -77,13 +77,26 @@ template <int NCT> struct MsGeom {
 __device__ __forceinline__ f32x4 mfma16x16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma16x16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
-// FAST: the 24x24 map of the 768x768 plans (H, W compile-time: row offsets of the depthwise window are instruction immediates)
+// four 16-bit values as the depthwise window holds them in registers (8 bytes: one ds_read_b64), widened where they are used
+template <typename T> struct Raw4;
+template <> struct Raw4<__bf16> { using type = bf16x4; };
+template <> struct Raw4<_Float16> { using type = f16x4; };
+template <typename V> __device__ __forceinline__ f32x4 widen4(V v) { return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
+template <int N> struct MsInt { static constexpr int value = N; };
+
+// FORM of the kernel: MS_GENERAL (any map that fits, whole or in bands; every width and row count a runtime value), MS_MAP24 (FAST below:
+// the whole 24x24 map of the 768x768 plans, H and W compile-time) and MS_BAND48 (the bands of a 48-wide map, the other shape of those
+// plans: W compile-time).  With a compile-time width the row offsets of the depthwise window are instruction immediates and the
+// divisions are by constants.
+constexpr int MS_GENERAL = 0, MS_MAP24 = 1, MS_BAND48 = 2;
+
 // (Two forms of the SqueezeExcitation INSIDE this launch were built, measured and removed: round 4's FTC_FLAG_SE_INLINE -- gated output, plain
 // project GEMM: 60.0 vs 41.7 + 14.9 us -- and round 5's FTC_FLAG_SE_TAIL -- ungated output, the last workgroups of an image fold the project
 // weights: 61.9 vs 42.5 + 14.8 us on one stream and waits that run into their bound under two lanes; profiles/r04_mbhead_se_inline_experiment.txt,
 // profiles/r05_se_tail_experiment.txt, DESIGN.md appendix.)
-template <typename T, bool FAST, int NCT = 4>
+template <typename T, int FORM, int NCT = 4>
 __global__ __launch_bounds__(MS_NT, 2) void mbconv_slice_kernel(const MbsP p) {
+    constexpr bool FAST = FORM == MS_MAP24;
     using GM = MsGeom<NCT>;
     constexpr int MS_CC = GM::CC, MS_STAGE = GM::STAGE, MS_PITCH = GM::PITCH, MS_CONST = GM::CONST, CQN = GM::CQN, NPL = GM::NPL;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -98,7 +111,7 @@ __global__ __launch_bounds__(MS_NT, 2) void mbconv_slice_kernel(const MbsP p) {
     const int c0 = sl * MS_CC;
     // Band mode (maps larger than 576 pixels: the 48x48 stages): the workgroup owns the output rows [y0, y1) of its image and holds the
     // expanded rows [ylo, yhi) = one halo row above and below (recomputed by the neighbouring band); H below = the rows it HOLDS.
-    const int W = FAST ? 24 : p.W;
+    const int W = FAST ? 24 : FORM == MS_BAND48 ? 48 : p.W;
     const int y0 = FAST ? 0 : band * p.R, y1 = FAST ? 24 : min(p.H, y0 + p.R);
     const int ylo = FAST ? 0 : max(0, y0 - 1), yhi = FAST ? 24 : min(p.H, y1 + 1);
     const int H = yhi - ylo;
@@ -253,42 +266,110 @@ __global__ __launch_bounds__(MS_NT, 2) void mbconv_slice_kernel(const MbsP p) {
     f32x4 sum = {0.f, 0.f, 0.f, 0.f};
     T* outp = reinterpret_cast<T*>(p.out) + ((size_t)b * Mfull + (size_t)ylo * W) * p.C + c;
     const unsigned char* zslot = smem_raw + cq * 8;             // slot 0: zeros
-    for (int s = dw_on ? pl : nstrips; s < nstrips; s += NPL) {
-        const int sr = s / W, x = s - sr * W;
-        const int oy0 = yo + sr * MS_R;
-        // window rows 0..6 from base0, 7.. from base1: the immediate offset of a DS instruction is 16 bits
-        const unsigned char* base0 = smem_raw + ((oy0 - 1) * W1 + x) * MS_PITCH + cq * 8;      // slot of (oy0 - 1, x - 1)
-        const unsigned char* base1 = base0 + 7 * W1 * MS_PITCH;
-        f32x4 a[MS_R];
+    // A strip = NR outputs of one column (NR = MS_R, fewer in the last strip row of a band: only rows that are stored are computed, where
+    // the first version ran every strip MS_R tall and guarded the stores -- 12 rows of reads and FMAs per 10 stored in the bands of the
+    // 48x48 maps).  Its window is (NR + 2) rows x 3 slots, raw 16-bit (48 registers; the GEMM accumulators are dead here).  Rows 1..NR of
+    // the window are rows the strip stores, inside the image by construction; only the first and the last row can lie outside it and
+    // read the zero slot instead.  With a select on every row's address (first version of the general form) the compiler kept each
+    // row's three reads behind the row before -- eight dependent LDS round trips per strip; with two, it requests the whole window at
+    // the top of the strip and consumes it behind counted lgkmcnt waits, as it always did in the 24x24 form.  (Requesting the NEXT
+    // strip's window by hand under this strip's SiLU, order pinned with sched_barrier, was measured slower: DESIGN.md appendix A11.)
+    using R4 = typename Raw4<T>::type;
+    // the lane's strips s, s + NPL, .. below lim, all NR outputs tall; returns the first strip it did not run
+    auto run_strips = [&](auto nr_c, int s, const int lim) __attribute__((always_inline)) {
+        constexpr int NR = decltype(nr_c)::value;
+        for (; s < lim; s += NPL) {
+            const int sr = s / W, x = s - sr * W;
+            const int oy0 = yo + sr * MS_R;
+            // window rows 0..6 from base0, 7.. from base1: the immediate offset of a DS instruction is 16 bits
+            const unsigned char* base0 = smem_raw + ((oy0 - 1) * W1 + x) * MS_PITCH + cq * 8;      // slot of (oy0 - 1, x - 1)
+            const unsigned char* base1 = base0 + 7 * W1 * MS_PITCH;
+            R4 win[(NR + 2) * 3];
 #pragma unroll
-        for (int oo = 0; oo < MS_R; ++oo) a[oo] = bv;
+            for (int r = 0; r < NR + 2; ++r) {
+                const bool rok = r == 0 ? oy0 > 0 : r == NR + 1 ? oy0 + NR < H : true;
+                const unsigned char* rp = (r < 7 ? base0 + r * W1 * MS_PITCH : base1 + (r - 7) * W1 * MS_PITCH);
 #pragma unroll
-        for (int r = 0; r < MS_R + 2; ++r) {
-            bool rok;                                           // FAST: rows 1..R of a strip are inside the 24-row map by construction
-            if (FAST) rok = r == 0 ? oy0 > 0 : r == MS_R + 1 ? oy0 + MS_R < 24 : true;
-            else rok = (unsigned)(oy0 - 1 + r) < (unsigned)H;
-            const unsigned char* rp = (r < 7 ? base0 + r * W1 * MS_PITCH : base1 + (r - 7) * W1 * MS_PITCH);
-            f32x4 xin[3];
+                for (int s2 = 0; s2 < 3; ++s2) win[r * 3 + s2] = *reinterpret_cast<const R4*>(rok ? rp + s2 * MS_PITCH : zslot);
+            }
+            f32x4 a[NR];
 #pragma unroll
-            for (int s2 = 0; s2 < 3; ++s2) xin[s2] = load4<T>(reinterpret_cast<const T*>(rok ? rp + s2 * MS_PITCH : zslot));
+            for (int oo = 0; oo < NR; ++oo) a[oo] = bv;
 #pragma unroll
-            for (int oo = 0; oo < MS_R; ++oo) {
-                const int kr = r - oo;
-                if (kr >= 0 && kr < 3) {
+            for (int r = 0; r < NR + 2; ++r) {
+                f32x4 xin[3];
 #pragma unroll
-                    for (int s2 = 0; s2 < 3; ++s2)
+                for (int s2 = 0; s2 < 3; ++s2) xin[s2] = widen4(win[r * 3 + s2]);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) a[oo][e] = fmaf(wv[kr * 3 + s2][e], xin[s2][e], a[oo][e]);
+                for (int oo = 0; oo < NR; ++oo) {
+                    const int kr = r - oo;
+                    if (kr >= 0 && kr < 3) {
+#pragma unroll
+                        for (int s2 = 0; s2 < 3; ++s2)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) a[oo][e] = fmaf(wv[kr * 3 + s2][e], xin[s2][e], a[oo][e]);
+                    }
                 }
             }
-        }
 #pragma unroll
-        for (int oo = 0; oo < MS_R; ++oo) {
-            const int oy = oy0 + oo;
-            if (FAST || oy < yend) {
+            for (int oo = 0; oo < NR; ++oo) {
                 a[oo] = act_silu_fast4(a[oo]);
-                store4<T>(outp + (oy * W + x) * p.C, a[oo]);
+                store4<T>(outp + ((oy0 + oo) * W + x) * p.C, a[oo]);
                 sum += a[oo];
+            }
+        }
+        return s;
+    };
+    {
+        int s = dw_on ? pl : nstrips;
+        if constexpr (FAST) {
+            // the 24x24 form: 4 x 24 strips, all MS_R tall, every bound a constant.  Its strip loop is kept as it was (the compiler always
+            // requested its whole window at the top of a strip), so that these instantiations compile to the code they were
+            for (; s < nstrips; s += NPL) {
+                const int sr = s / W, x = s - sr * W;
+                const int oy0 = yo + sr * MS_R;
+                // window rows 0..6 from base0, 7.. from base1: the immediate offset of a DS instruction is 16 bits
+                const unsigned char* base0 = smem_raw + ((oy0 - 1) * W1 + x) * MS_PITCH + cq * 8;      // slot of (oy0 - 1, x - 1)
+                const unsigned char* base1 = base0 + 7 * W1 * MS_PITCH;
+                f32x4 a[MS_R];
+#pragma unroll
+                for (int oo = 0; oo < MS_R; ++oo) a[oo] = bv;
+#pragma unroll
+                for (int r = 0; r < MS_R + 2; ++r) {
+                    const bool rok = r == 0 ? oy0 > 0 : r == MS_R + 1 ? oy0 + MS_R < 24 : true;      // rows 1..R of a strip are inside the 24-row map by construction
+                    const unsigned char* rp = (r < 7 ? base0 + r * W1 * MS_PITCH : base1 + (r - 7) * W1 * MS_PITCH);
+                    f32x4 xin[3];
+#pragma unroll
+                    for (int s2 = 0; s2 < 3; ++s2) xin[s2] = load4<T>(reinterpret_cast<const T*>(rok ? rp + s2 * MS_PITCH : zslot));
+#pragma unroll
+                    for (int oo = 0; oo < MS_R; ++oo) {
+                        const int kr = r - oo;
+                        if (kr >= 0 && kr < 3) {
+#pragma unroll
+                            for (int s2 = 0; s2 < 3; ++s2)
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) a[oo][e] = fmaf(wv[kr * 3 + s2][e], xin[s2][e], a[oo][e]);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int oo = 0; oo < MS_R; ++oo) {
+                    a[oo] = act_silu_fast4(a[oo]);
+                    store4<T>(outp + ((oy0 + oo) * W + x) * p.C, a[oo]);
+                    sum += a[oo];
+                }
+            }
+        } else {
+            // every strip row but the last is MS_R tall; the last has the rows that remain (10-row bands: 4; the 8-row last band of a 48-row map: 2)
+            const int hl = (yend - yo) - (nsr - 1) * MS_R;
+            s = run_strips(MsInt<MS_R>{}, s, hl == MS_R ? nstrips : nstrips - W);
+            switch (hl) {
+                case 1: run_strips(MsInt<1>{}, s, nstrips); break;
+                case 2: run_strips(MsInt<2>{}, s, nstrips); break;
+                case 3: run_strips(MsInt<3>{}, s, nstrips); break;
+                case 4: run_strips(MsInt<4>{}, s, nstrips); break;
+                case 5: run_strips(MsInt<5>{}, s, nstrips); break;
+                default: break;
             }
         }
     }
@@ -369,6 +450,9 @@ int ftc_mbhead_band_rows(int H, int W) {
 // the FAST instantiation holds the whole 24x24 map in one workgroup (one band).  0x100: the general kernel (tests)
 bool ftc_mbhead_whole_map(const ftc_op& o) { return o.H == 24 && o.W == 24 && ftc_mbhead_bands(o) == 1 && !(o.flags & 0x100); }
 
+// the band form of the 48-wide maps (stages 4-5 of the 768x768 plans).  0x100: the general kernel (tests)
+static bool ftc_mbhead_band48(const ftc_op& o) { return o.aux1 > 0 && o.W == 48 && !(o.flags & 0x100); }
+
 hipError_t launch_mbhead_x3(const OpArgs& a, hipStream_t s);
 
 hipError_t launch_mbhead(const OpArgs& a, hipStream_t s) {
@@ -386,13 +470,14 @@ hipError_t launch_mbhead(const OpArgs& a, hipStream_t s) {
     p.tl = (o.flags & 0x1000) ? reinterpret_cast<unsigned long long*>(const_cast<void*>(a.in2)) : nullptr;      // phase timeline (tools/mbslice_bench.py)
     const int slice = ftc_mbhead_slice(o);
     const int nblk = o.B * p.nb * (o.Cout / slice);
-    const bool fast = ftc_mbhead_whole_map(o);
+    const int form = ftc_mbhead_whole_map(o) ? MS_MAP24 : ftc_mbhead_band48(o) ? MS_BAND48 : MS_GENERAL;
     hipError_t e = hipSuccess;
 #define MBS_LAUNCH(T, F, N) do {                                                                                                   \
         if ((e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(mbconv_slice_kernel<T, F, N>), MsGeom<N>::LDS)) == hipSuccess) \
             hipLaunchKernelGGL((mbconv_slice_kernel<T, F, N>), dim3(nblk), dim3(MS_NT), MsGeom<N>::LDS, s, p);                  \
     } while (0)
-#define MBS_PICK(T, N) do { if (fast) MBS_LAUNCH(T, true, N); else MBS_LAUNCH(T, false, N); } while (0)
+#define MBS_PICK(T, N) do { if (form == MS_MAP24) MBS_LAUNCH(T, MS_MAP24, N); else if (form == MS_BAND48) MBS_LAUNCH(T, MS_BAND48, N); \
+                            else MBS_LAUNCH(T, MS_GENERAL, N); } while (0)
     if (o.in_dtype == FTC_F16) { if (slice == 96) MBS_PICK(_Float16, 3); else MBS_PICK(_Float16, 4); }
     else { if (slice == 96) MBS_PICK(__bf16, 3); else MBS_PICK(__bf16, 4); }
 #undef MBS_PICK
