@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libftc_hip.so")
 
-FTC_ABI_VERSION = 11
+FTC_ABI_VERSION = 12
 F32, BF16, F16 = 0, 1, 2
 (BASE_NULL, BASE_WORKSPACE, BASE_WEIGHTS, BASE_INPUT, BASE_HEATMAP, BASE_FEATURES, BASE_GRADS, NUM_BASES) = range(8)
 OP_STEM, OP_CONV, OP_DWCONV, OP_SE, OP_UPCAT, OP_NMS, OP_TAPSUM, OP_BNSTAT, OP_BNACT = 1, 2, 3, 4, 5, 6, 7, 8, 9
@@ -26,7 +26,7 @@ FLAG_PRESPLIT = 0x20000000
 MBHEAD_SLICE = 128
 
 EXPORTS = ["ftc_abi_version", "ftc_last_error", "ftc_device_info", "ftc_plan_create", "ftc_plan_destroy",
-           "ftc_plan_num_ops", "ftc_plan_run", "ftc_plan_run_streams", "ftc_plan_profile", "ftc_op_kernel_label", "ftc_decode_scratch_bytes", "ftc_decode", "ftc_tile_gather", "ftc_paste_maps",
+           "ftc_plan_num_ops", "ftc_plan_run", "ftc_plan_run_streams", "ftc_plan_profile", "ftc_op_kernel_label", "ftc_conv_signature", "ftc_tune_ops", "ftc_decode_scratch_bytes", "ftc_decode", "ftc_tile_gather", "ftc_paste_maps",
            "ftc_page_merge_scratch_bytes", "ftc_box_hists", "ftc_page_order_scratch_bytes", "ftc_page_order", "ftc_page_merge", "ftc_page_merge_variant", "ftc_adamw_schedulefree_step",
            "ftc_create", "ftc_destroy", "ftc_weights_bytes", "ftc_weights_host", "ftc_weights_offset", "ftc_workspace_bytes", "ftc_forward",
            "ftc_model_plan", "ftc_model_op_info", "ftc_plan_op",
@@ -149,6 +149,8 @@ def load():
     lib.ftc_plan_run_streams.argtypes = [vp, C.POINTER(vp), vp, vp, i32, i32]
     lib.ftc_plan_profile.argtypes = [vp, C.POINTER(vp), vp, C.POINTER(C.c_float)]
     lib.ftc_op_kernel_label.argtypes = [C.POINTER(Op), C.c_char_p, i32]
+    lib.ftc_conv_signature.argtypes = [C.POINTER(Op), C.c_char_p, i32]
+    lib.ftc_tune_ops.argtypes = [C.POINTER(Op), i32]
     lib.ftc_decode_scratch_bytes.argtypes = [i32, i32, i32]
     lib.ftc_decode_scratch_bytes.restype = i64
     lib.ftc_decode.argtypes = [vp, vp, i32, i32, i32, i32, vp, C.c_float, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp]

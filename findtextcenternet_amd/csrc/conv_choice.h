@@ -10,7 +10,8 @@
 //   bit  7     (with bit 6 and FTC_FLAG_W_FRAG weights) its weights-through-L1 successor
 //   bits 8-9   K step: 1 = 32, 2 = 64, 3 = 128; on the halo kernel 1 = 64-byte rows
 //   bits 10-11 intra-workgroup split-K of the register-staged kernel: 1 = 2 groups, 2 = 4 groups
-// The Python side fills it from a table measured on MI355X (findtextcenternet_amd/tuning.py); the choices compute the same convolution --
+// plan.hip fills it from a table measured on MI355X by findtextcenternet_amd/tuning.py (apply_tuning: for the plans of ftc_forward and, through
+// ftc_tune_ops, for a caller's op array such as the train step's); the choices compute the same convolution --
 // bit-identical among the tile configs and stagings (same K order), in another fp32 summation order with split-K and on the 144-pixel tiles.
 //
 // Hints that plan creation ACCEPTS but that are not honoured (none is produced by tuning.candidates; whether to refuse them is an ABI

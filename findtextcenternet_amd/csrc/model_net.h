@@ -2,8 +2,9 @@
 //   pack.hip   the weight packing (once per checkpoint): eval-mode BatchNorm folded into the preceding convolution in float64,
 //              K-major [Cout][kh*kw][Cin] re-layout, conversion to the MFMA compute type, one blob
 //   plan.hip   the plan builder (once per input shape and switch setting): the plan switches, the per-shape op list with its
-//              liveness-based activation arena, and the measured kernel selection (tuning_table.inc)
-//   model.hip  ftc_model, the plan caches and the extern "C" entry points
+//              liveness-based activation arena, and the measured kernel selection (the table key and the lookup, also exported for a
+//              caller's own op array: ftc_conv_signature, ftc_tune_ops)
+//   model.hip  ftc_model, the plan caches and the extern "C" entry points of the model
 // and the network description all of them read (what the reference expresses as nn.Module composition -- CenterNetDetection.forward,
 // models/detector.py:217-230 = stem + 100 Fused-MBConv / MBConv blocks with taps (BackboneModel.forward :139-146,
 // config rows :12-28) + nine Leafmap heads (:148-201) -- followed by the NMS of CenterNetDetector.forward (:289-296)).

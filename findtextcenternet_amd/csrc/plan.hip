@@ -1,5 +1,6 @@
 // The plan builder behind ftc_forward (once per input shape and switch setting): the plan switches, the decision of every backbone block's
-// form, the op list with its liveness-based activation arena, and the measured kernel selection (tuning_table.inc).
+// form, the op list with its liveness-based activation arena, and the measured kernel selection: what a table key is and which hint an op
+// adopts are decided here alone (ftc_conv_signature / ftc_tune_ops give the same answers to the train step and the tuner).
 // Host-only code: no kernels here.  Compiled with -ffp-contract=off like pack.hip: the flops / bytes figures of ftc_op_info are sums of
 // products in float64 and stay the same between builds.
 #include <cstdlib>
@@ -14,7 +15,7 @@ namespace {
 // ---- measured kernel selection ----------------------------------------------------------------------
 struct TuneEntry { const char* sig; int aux0; };
 const TuneEntry kTuning[] = {
-#include "tuning_table.inc"
+#include "build/tuning_table.inc"       // written by build.py from tuning_gfx950.json
     {nullptr, 0}};
 
 // The measured choices by signature, with the entries of the FTC_TUNING_OVERRIDE file, if any, merged in: built when the first plan that
@@ -48,10 +49,13 @@ std::string conv_signature(const ftc_op& o, bool strip_split = false) {
     return buf;
 }
 
-void apply_tuning(std::vector<ftc_op>& ops, const PlanOptions& opt) {
-    if (opt.no_tuning) return;
+// Returns how many ops took a table entry
+int apply_tuning(ftc_op* ops, int n_ops, const PlanOptions& opt) {
+    if (opt.no_tuning) return 0;
     const std::map<std::string, int>& table = tuning_table();
-    for (ftc_op& o : ops) {
+    int n = 0;
+    for (int i = 0; i < n_ops; ++i) {
+        ftc_op& o = ops[i];
         if (o.kind != FTC_OP_CONV) continue;
         auto it = table.find(conv_signature(o));
         if (it == table.end() && (o.flags & FTC_FLAG_SPLIT16)) it = table.find(conv_signature(o, true));     // fp16x3 without its own measurement: the fp32 choice
@@ -63,7 +67,9 @@ void apply_tuning(std::vector<ftc_op>& ops, const PlanOptions& opt) {
         const int keep = o.aux0;
         o.aux0 = it->second;
         if (conv_validate(o) != nullptr) o.aux0 = keep;
+        else ++n;
     }
+    return n;
 }
 
 }  // namespace
@@ -728,7 +734,7 @@ int Builder::finish(ModelPlan* out, int mh, int mw) {
         o.scale = res(s.scale); o.shift = res(s.shift); o.aux = res(s.aux); o.out2 = res(s.out2);
         out->plan.ops.push_back(o);
     }
-    apply_tuning(out->plan.ops, opt_);             // measured kernel choice per conv shape (ftc_op.aux0)
+    apply_tuning(out->plan.ops.data(), (int)out->plan.ops.size(), opt_);             // measured kernel choice per conv shape (ftc_op.aux0)
     out->plan.workspace_bytes = align_up(top);
     out->plan.weights_bytes = (int64_t)m_->blob.bytes.size();
     out->meta = meta_;
@@ -746,3 +752,21 @@ int build_model_plan(ftc_model* m, int B, int H, int W, bool nchw, const PlanOpt
 int build_decoder_plan(ftc_model* m, int rows, const PlanOptions& opt, ModelPlan* out) { return Builder(m, 1, rows, 1, false, opt).build_decoder(out); }
 
 }  // namespace ftc_model_detail
+
+extern "C" {
+
+int ftc_conv_signature(const ftc_op* op, char* buf, int len) {
+    if (!op || !buf) return ftc_set_error(FTC_ERR_INVALID, "ftc_conv_signature: null arguments");
+    if (op->kind != FTC_OP_CONV) return ftc_set_error(FTC_ERR_INVALID, "ftc_conv_signature: not an FTC_OP_CONV");
+    const std::string sig = ftc_model_detail::conv_signature(*op);
+    if (len <= (int)sig.size()) return ftc_set_error(FTC_ERR_INVALID, "ftc_conv_signature: buffer too short for " + sig);
+    std::memcpy(buf, sig.c_str(), sig.size() + 1);
+    return FTC_OK;
+}
+
+int ftc_tune_ops(ftc_op* ops, int n_ops) {
+    if (!ops || n_ops < 0) return ftc_set_error(FTC_ERR_INVALID, "ftc_tune_ops: null / negative arguments");
+    return ftc_model_detail::apply_tuning(ops, n_ops, ftc_model_detail::read_plan_options());
+}
+
+}  // extern "C"

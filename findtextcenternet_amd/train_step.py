@@ -369,10 +369,11 @@ class TrainStep:
                 gx = g.dgrad(gz0, ho, wo, cout, b + ".0.0.weight", c_, 3, stride, h_, w_, add=skip)
         g.join()
         ops, ws = g.resolve()
-        from . import tuning
-        tuning.apply(ops)                                   # measured kernel choice per conv signature (tuning_gfx950.json; FTC_NO_TUNING=1: heuristics)
+        lib = L.load()
+        # measured kernel choice per convolution, as ftc_forward's plans get it (csrc/plan.hip); returns how many took one
+        L.check(min(lib.ftc_tune_ops(ops, len(ops)), 0), "ftc_tune_ops (train step)")
         h = C.c_void_p()
-        L.check(L.load().ftc_plan_create(ops, len(ops), ws, self.blob.numel(), C.byref(h)), "ftc_plan_create (train step)")
+        L.check(lib.ftc_plan_create(ops, len(ops), ws, self.blob.numel(), C.byref(h)), "ftc_plan_create (train step)")
         return dict(handle=h, workspace_bytes=ws, n_ops=len(ops), ops=ops, maps=maps[1], feats=feats[1], keep=fwd["keep"][1], res_names=fwd["res_names"],
                     mh=mh, mw=mw, sel=sel[1], lab=lab[1], idm=idm[1], lossv=lossv[1], alphas=alphas[1], n_rows=n_rows, n_fwd=n_fwd,
                     loss_bwd_op=lscale_slot, names=g.names, dec_outs=[d["out"][1] for d in dec])

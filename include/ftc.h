@@ -41,8 +41,9 @@ extern "C" {
    9: FTC_FLAG_SE_INLINE removed (flag bit 0x20000000 is free again); FTC_MBHEAD_MAX_SQUEEZE; KBLOCK32 validation on CONV;
       ftc_page_merge_variant (the demo script's selection + two-pass seed rows)
    10: FTC_OP_FMBCONV (Fused-MBConv block with expansion in one launch: 3x3 expand + SiLU + 1x1 project + residual)
-   11: glyph code-point decode: ftc_glyph_select, ftc_glyph_decode_workspace_bytes, ftc_glyph_decode */
-#define FTC_ABI_VERSION 11
+   11: glyph code-point decode: ftc_glyph_select, ftc_glyph_decode_workspace_bytes, ftc_glyph_decode
+   12: ftc_conv_signature, ftc_tune_ops (the measured kernel selection of ftc_forward's plans, for a caller's own op array) */
+#define FTC_ABI_VERSION 12
 
 typedef enum ftc_status {
     FTC_OK = 0,
@@ -338,6 +339,19 @@ int ftc_plan_profile(const ftc_plan* plan, void* const bases[FTC_NUM_BASES], voi
 /* Label of the kernel instantiation an op dispatches to (dtype + tile configuration), e.g.
    "conv_igemm<bf16,in=bf16,out=bf16,tile=192x128>"; used to attribute rocprof / HIP-event time. */
 int ftc_op_kernel_label(const ftc_op* op, char* buf, int len);
+
+/* The measured kernel selection (ftc_op.aux0 of FTC_OP_CONV), as the plans of ftc_forward get it.
+   ftc_conv_signature writes the key under which a convolution is looked up in the table of measured choices: its dtypes (fp16 reads as
+   bf16: same kernels, same rate), shape, activation and flags without FTC_FLAG_KBLOCK32 and FTC_FLAG_PRESPLIT, e.g.
+   "w1i1o1_B8_192x192_c96of96_n384of384_k3s1_f0_a1".  FTC_ERR_INVALID for a null argument, an op that is no FTC_OP_CONV, or a buffer
+   too short for the key and its terminator (192 bytes always hold it).
+   ftc_tune_ops sets aux0 of every FTC_OP_CONV of ops[0..n_ops) that has an entry in the table compiled into the library (with the lines
+   "signature aux0" of the file FTC_TUNING_OVERRIDE names merged on top; an op with FTC_FLAG_SPLIT16 and no entry of its own takes the
+   entry of the same op without the flag) -- but only if the op validates with that value: otherwise, and for an op without an entry,
+   aux0 stays as the caller set it.  With FTC_NO_TUNING set (to anything but "" or "0") it changes nothing.  Returns the number of ops
+   whose aux0 it set, or a negative ftc_status. */
+int ftc_conv_signature(const ftc_op* op, char* buf, int len);
+int ftc_tune_ops(ftc_op* ops, int n_ops);
 
 /* Model ------------------------------------------------------------------------------------ */
 /*

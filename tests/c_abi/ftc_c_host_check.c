@@ -1,7 +1,7 @@
 /*
  * Host-only walk over the C ABI for a sanitizer build (ASan / UBSan run of the shim): everything include/ftc.h
  * does on the HOST -- checkpoint folding and packing (ftc_create, all four precisions), plan building and validation for several
- * shapes, op introspection, kernel labels, the bounded decoder-plan cache (more row counts than it holds: eviction), error paths
+ * shapes, op introspection, kernel labels, the measured kernel selection on a caller's op array, the bounded decoder-plan cache (more row counts than it holds: eviction), error paths
  * (bad arguments, missing tensors, invalid ops) -- without touching a device.  tests/test_c_abi.py builds the library's host
  * translation units (model.hip, ftc_api.hip) and this file with -fsanitize=address,undefined and runs it.
  *
@@ -67,6 +67,8 @@ int main(int argc, char** argv) {
             const ftc_plan* plan = NULL;
             ftc_plan_info info;
             CHECK(ftc_model_plan(m, B, H, W, 0, &plan, &info) == FTC_OK && info.n_ops > 250 && info.map_h == H / 4);
+            ftc_op three[3];                                                    /* op 0 (the stem) and the first two convolutions */
+            int n_three = 1;
             for (int i = 0; i < info.n_ops; ++i) {
                 ftc_op op;
                 ftc_op_info oi;
@@ -74,8 +76,29 @@ int main(int argc, char** argv) {
                 CHECK(ftc_plan_op(plan, i, &op) == FTC_OK && ftc_model_op_info(m, B, H, W, 0, i, &oi) == FTC_OK);
                 CHECK(ftc_op_kernel_label(&op, label, sizeof label) == FTC_OK);
                 checksum += op.kind + (long)strlen(label) + (long)(oi.flops / 1e6);
+                if (i == 0) three[0] = op;
+                else if (op.kind == FTC_OP_CONV && n_three < 3) three[n_three++] = op;
             }
             CHECK(ftc_plan_op(plan, info.n_ops, &junk) != FTC_OK);             /* out of range */
+            /* the measured kernel selection on a caller's array: the plan's own ops keep the choices the library gave them */
+            CHECK(n_three == 3 && three[0].kind != FTC_OP_CONV);
+            const int hints[2] = {three[1].aux0, three[2].aux0};
+            const int tuned = ftc_tune_ops(three, 3);
+            CHECK(tuned >= 0 && tuned <= 2 && three[1].aux0 == hints[0] && three[2].aux0 == hints[1]);
+            CHECK(ftc_tune_ops(NULL, 3) == FTC_ERR_INVALID && ftc_tune_ops(three, -1) == FTC_ERR_INVALID && ftc_tune_ops(three, 0) == 0);
+            for (int k = 1; k < 3; ++k) {
+                char sig[192], small[10];
+                CHECK(ftc_conv_signature(&three[k], sig, sizeof sig) == FTC_OK && strlen(sig) > 10);
+                CHECK(ftc_conv_signature(&three[k], small, sizeof small) == FTC_ERR_INVALID);                 /* the short buffer */
+                char* exact = (char*)malloc(strlen(sig) + 1);                                               /* and one that just fits */
+                CHECK(ftc_conv_signature(&three[k], exact, (int)strlen(sig)) == FTC_ERR_INVALID);
+                CHECK(ftc_conv_signature(&three[k], exact, (int)strlen(sig) + 1) == FTC_OK && strcmp(exact, sig) == 0);
+                free(exact);
+                checksum += (long)strlen(sig);
+            }
+            char sig0[192];
+            CHECK(ftc_conv_signature(&three[0], sig0, sizeof sig0) == FTC_ERR_INVALID && ftc_conv_signature(NULL, sig0, sizeof sig0) == FTC_ERR_INVALID &&
+                  ftc_conv_signature(&three[1], NULL, 192) == FTC_ERR_INVALID);
         }
         CHECK(ftc_workspace_bytes(m, 1, 100, 100) == -1);                       /* not a multiple of 32 */
         for (int rows = 1; rows <= 40; ++rows)                                  /* 40 row counts through a cache of 16: eviction */

@@ -30,7 +30,7 @@ def _ops(plan):
 
 def _differences(a, b):
     """Fields in which two ops differ, leaving out the operand offsets (the two plans pin different buffers) and a convolution's aux0
-    (the train step writes the measured kernel choice there, tuning.apply)."""
+    (the train step has the library write the measured kernel choice there, ftc_tune_ops)."""
     d = [f for f in INT_FIELDS if getattr(a, f) != getattr(b, f) and not (f == "aux0" and a.kind == L.OP_CONV)]
     return d + [f for f in REF_FIELDS if getattr(a, f).base != getattr(b, f).base]
 

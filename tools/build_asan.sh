@@ -10,7 +10,7 @@ OUT="$CS/build/asan"
 mkdir -p "$OUT"
 for f in pack plan model ftc_api; do
   if [ ! -f "$OUT/$f.o" ] || [ "$CS/$f.hip" -nt "$OUT/$f.o" ] || [ "$ROOT/include/ftc.h" -nt "$OUT/$f.o" ] || [ "$CS/model_net.h" -nt "$OUT/$f.o" ] ||
-     [ "$CS/tuning_table.inc" -nt "$OUT/$f.o" ]; then
+     [ "$CS/build/tuning_table.inc" -nt "$OUT/$f.o" ]; then
     EXTRA=""; { [ "$f" = pack ] || [ "$f" = plan ]; } && EXTRA="-ffp-contract=off"       # as in build.py's EXTRA_FLAGS
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O1 -std=c++20 -fPIC -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-gpu-sanitize -fno-omit-frame-pointer -g $EXTRA -c "$CS/$f.hip" -o "$OUT/$f.o"
   fi
