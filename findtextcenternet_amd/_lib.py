@@ -61,6 +61,13 @@ SAMPLE_NEAREST, SAMPLE_BLANK, SAMPLE_COLOUR = 1, 2, 4
 SAMPLE_MONO, SAMPLE_SINGLE, SAMPLE_DOUBLE, SAMPLE_BACKGROUND = range(4)
 SAMPLE_EXPORTS = ["ftc_sample_abi_version", "ftc_sample_synth"]
 
+# include/ftc_sample_aug.h (the reference's random_salt / random_distortion on the device)
+FTC_SAMPLE_AUG_ABI_VERSION = 1
+DISTORT_NOISE, DISTORT_BLUR, DISTORT_SHARPEN = 1, 2, 4
+DISTORT_MAX_RADIUS = 32
+SAMPLE_AUG_EXPORTS = ["ftc_sample_aug_abi_version", "ftc_sample_synth_salt", "ftc_sample_distort_workspace_bytes", "ftc_sample_distort",
+                      "ftc_sample_normal_fill"]
+
 
 class FtcLibraryError(RuntimeError):
     pass
@@ -119,6 +126,17 @@ class SampleDesc(C.Structure):
                                  "dbl_top", "dbl_bottom", "dbl_left", "dbl_right", "bg_h", "bg_w", "bg_y0", "bg_x0")] + [
         ("fwd", C.c_float * 9), ("inv", C.c_float * 9), ("inv2", C.c_float * 9), ("startx", C.c_float), ("starty", C.c_float),
         ("fg1", C.c_float * 3), ("fg2", C.c_float * 3), ("bg", C.c_float * 3)]
+
+
+class SaltDesc(C.Structure):
+    """ftc_salt_desc of include/ftc_sample_aug.h: 24 bytes."""
+    _fields_ = [("grid", C.c_void_p)] + [(n, C.c_int32) for n in ("step", "grid_h", "grid_w", "reserved")]
+
+
+class DistortDesc(C.Structure):
+    """ftc_distort_desc of include/ftc_sample_aug.h: 304 bytes, no padding."""
+    _fields_ = [("noise", C.c_void_p), ("seed", C.c_uint64), ("alpha", C.c_double), ("w", C.c_double * (DISTORT_MAX_RADIUS + 1)),
+                ("flags", C.c_int32), ("radius", C.c_int32), ("k", C.c_float), ("reserved", C.c_int32)]
 
 
 _lib = None
@@ -228,6 +246,14 @@ def load():
     lib.ftc_features_at.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp]
     lib.ftc_sample_abi_version.restype = i32
     lib.ftc_sample_synth.argtypes = [C.POINTER(SampleDesc), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.ftc_sample_aug_abi_version.restype = i32
+    lib.ftc_sample_synth_salt.argtypes = [C.POINTER(SampleDesc), vp, C.POINTER(SaltDesc), vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.ftc_sample_distort_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.ftc_sample_distort_workspace_bytes.restype = i64
+    lib.ftc_sample_distort.argtypes = [C.POINTER(DistortDesc), vp, i32, i32, i32, vp, vp, i64, vp]
+    lib.ftc_sample_normal_fill.argtypes = [C.c_uint64, i64, vp, vp]
+    if lib.ftc_sample_aug_abi_version() != FTC_SAMPLE_AUG_ABI_VERSION:
+        raise FtcLibraryError(f"sample-aug ABI mismatch: library {lib.ftc_sample_aug_abi_version()} vs binding {FTC_SAMPLE_AUG_ABI_VERSION}")
     if lib.ftc_sample_abi_version() != FTC_SAMPLE_ABI_VERSION:
         raise FtcLibraryError(f"sample ABI mismatch: library {lib.ftc_sample_abi_version()} vs binding {FTC_SAMPLE_ABI_VERSION}")
     if lib.ftc_prep_abi_version() != FTC_PREP_ABI_VERSION:

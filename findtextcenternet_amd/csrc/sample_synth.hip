@@ -15,6 +15,7 @@
 #include "ftc_common.h"
 #include "ftc_host.h"
 #include "../../include/ftc_sample.h"
+#include "../../include/ftc_sample_aug.h"
 
 #pragma clang fp contract(off)
 
@@ -248,8 +249,10 @@ __global__ __launch_bounds__(256) void ss_map_kernel(const ftc_sample_desc* __re
     lab[4 * mapn + i] = sl;
 }
 
-// one thread per output pixel: resample, then the composition; the gray intermediate stays in a register
-__global__ __launch_bounds__(256) void ss_image_kernel(const ftc_sample_desc* __restrict__ descs, int H, int W, float* __restrict__ image) {
+// one thread per output pixel: resample, the salt (include/ftc_sample_aug.h; `salt` may be null), then the composition; the gray
+// intermediate stays in a register
+__global__ __launch_bounds__(256) void ss_image_kernel(const ftc_sample_desc* __restrict__ descs, const ftc_salt_desc* __restrict__ salt, int H, int W,
+                                                       float* __restrict__ image) {
     const int b = blockIdx.y;
     const int n = H * W;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -279,6 +282,11 @@ __global__ __launch_bounds__(256) void ss_image_kernel(const ftc_sample_desc* __
         const SsWeights w = ss_weights(rx, ry);
         a = ss_bilinear(w, ss_page(d, w.X, w.Y), ss_page(d, w.X + 1, w.Y), ss_page(d, w.X, w.Y + 1), ss_page(d, w.X + 1, w.Y + 1));
     }
+    if (salt && salt[b].grid) {
+        const ftc_salt_desc& sd = salt[b];
+        const unsigned code = sd.grid[(size_t)(y / sd.step) * sd.grid_w + x / sd.step];
+        a = code == 1u ? 0.f : (code == 2u ? 1.f : a);
+    }
     if (d.compose == FTC_SAMPLE_BACKGROUND) {
         const int yi = y + d.bg_y0, xi = x + d.bg_x0;
         const bool in = yi >= 0 && yi < d.bg_h && xi >= 0 && xi < d.bg_w;
@@ -297,6 +305,8 @@ int ss_hip_fail(hipError_t e, const char* what) { return ftc_set_error(FTC_ERR_H
 
 int ss_bad(int b, const char* what) { return ftc_set_error(FTC_ERR_INVALID, "ftc_sample_synth: descriptor " + std::to_string(b) + ": " + what); }
 
+int ss_bad_salt(int b, const char* what) { return ftc_set_error(FTC_ERR_INVALID, "ftc_sample_synth_salt: salt record " + std::to_string(b) + ": " + what); }
+
 }  // namespace
 
 extern "C" {
@@ -305,6 +315,11 @@ int ftc_sample_abi_version(void) { return FTC_SAMPLE_ABI_VERSION; }
 
 int ftc_sample_synth(const ftc_sample_desc* descs_host, const ftc_sample_desc* descs_dev, int B, int H, int W, int scale, float* image, float* labelmap,
                      int32_t* idmap, float* minsize, void* stream) {
+    return ftc_sample_synth_salt(descs_host, descs_dev, nullptr, nullptr, B, H, W, scale, image, labelmap, idmap, minsize, stream);
+}
+
+int ftc_sample_synth_salt(const ftc_sample_desc* descs_host, const ftc_sample_desc* descs_dev, const ftc_salt_desc* salt_host, const ftc_salt_desc* salt_dev,
+                          int B, int H, int W, int scale, float* image, float* labelmap, int32_t* idmap, float* minsize, void* stream) {
     if (!descs_host || !descs_dev || !image || !labelmap || !idmap || !minsize) return ftc_set_error(FTC_ERR_INVALID, "ftc_sample_synth: null pointer argument");
     if (B < 1 || B > 65535) return ftc_set_error(FTC_ERR_INVALID, "ftc_sample_synth: B outside 1..65535");
     if (H < 32 || W < 32 || H % 32 || W % 32 || H > 16384 || W > 16384 || scale < 2 || scale % 2 || H % scale || W % scale)
@@ -327,13 +342,21 @@ int ftc_sample_synth(const ftc_sample_desc* descs_host, const ftc_sample_desc* d
             return ss_bad(b, "bad page size");
         if (d.n_glyphs > max_glyphs) max_glyphs = d.n_glyphs;
     }
+    if (!salt_host != !salt_dev) return ftc_set_error(FTC_ERR_INVALID, "ftc_sample_synth_salt: the salt table needs its host and its device copy");
+    for (int b = 0; salt_host && b < B; ++b) {
+        const ftc_salt_desc& sd = salt_host[b];
+        if (!sd.grid) continue;
+        if (descs_host[b].flags & FTC_SAMPLE_COLOUR) return ss_bad_salt(b, "salt on a colour-variant sample");
+        if (sd.step < 1) return ss_bad_salt(b, "step < 1");
+        if (sd.grid_h < (H + sd.step - 1) / sd.step || sd.grid_w < (W + sd.step - 1) / sd.step) return ss_bad_salt(b, "grid smaller than ceil(H / step) x ceil(W / step)");
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int mapn = (H / scale) * (W / scale);
     const dim3 map_grid((mapn + 255) / 256, B), img_grid((H * W + 255) / 256, B);
     hipLaunchKernelGGL(ss_init_kernel, map_grid, dim3(256), 0, s, mapn, labelmap, idmap, minsize);
     if (max_glyphs > 0) hipLaunchKernelGGL(ss_glyph_kernel, dim3(max_glyphs, B), dim3(256), 0, s, descs_dev, H, W, scale, labelmap, idmap, minsize);
     hipLaunchKernelGGL(ss_map_kernel, map_grid, dim3(256), 0, s, descs_dev, H, W, scale, labelmap, minsize);
-    hipLaunchKernelGGL(ss_image_kernel, img_grid, dim3(256), 0, s, descs_dev, H, W, image);
+    hipLaunchKernelGGL(ss_image_kernel, img_grid, dim3(256), 0, s, descs_dev, salt_dev, H, W, image);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? FTC_OK : ss_hip_fail(e, "ftc_sample_synth");
 }

@@ -7,8 +7,12 @@ All randomness stays on the host: ``draw_crop_params`` / ``draw_colour_params`` 
 ``numpy.random.Generator`` and hand plain numbers (``CropParams``, ``ColourParams``) to ``SampleSynth``; the device work is a pure,
 bit-reproducible function of (pages, parameters).  There is no CPU fallback.
 
-Out of scope, and left with the caller: the reference's ``random_salt`` and ``random_distortion`` (NumPy RNG noise and scipy blurs on
-the finished image)."""
+The reference's loader then applies ``random_salt`` (before the colouring) and ``random_distortion`` (after it;
+``dataset/data_detector.py:17-41``).  Both run on the device too (include/ftc_sample_aug.h): ``draw_salt_params`` /
+``draw_distort_params`` make the reference's draws on the host (``draw_augment`` in ``transforms3``'s order, scaled by ``host_minsize``),
+``SampleSynth.__call__`` takes them as ``salt_params`` / ``distort_params``, and ``SampleSynth.distort`` applies the distortion to an image
+the caller already has.  The normal field of the noise is named by a 64-bit seed (Philox4x32-10 + Box-Muller on the device) or passed
+explicitly; numpy's own normal stream is not reproduced."""
 from __future__ import annotations
 
 import ctypes as C
@@ -104,6 +108,99 @@ class ColourParams:
     rect: Tuple[int, int, int, int] = (0, 0, 0, 0)
     bg_image: Optional["torch.Tensor"] = None
     bg_offset: Tuple[int, int] = (0, 0)
+
+
+@dataclass
+class SaltParams:
+    """One ``random_salt``: ``grid`` uint8 [gh, gw] (NumPy, or a tensor already on the GPU) of codes 0 keep / 1 black / 2 white, each
+    covering a ``step`` x ``step`` block of the gray crop."""
+    step: int
+    grid: "np.ndarray | torch.Tensor"
+
+
+@dataclass
+class DistortParams:
+    """One ``random_distortion``.  ``alpha`` None: no noise; else im += alpha * n with n the explicit ``noise`` tensor ([3, H, W] fp32 on the
+    GPU) or, when that is None, the device's normal field of ``seed``.  ``mode`` "none" / "blur" (Gaussian of ``sigma``) / "sharpen" (im +
+    ``k`` * (im - Gaussian of ``sigma``)).  ``weights`` = (radius, w) overrides ``gaussian_weights(sigma)`` (tests feed recorded ones)."""
+    alpha: Optional[float] = None
+    seed: int = 0
+    noise: Optional["torch.Tensor"] = None
+    sigma: float = 0.0
+    k: float = 0.0
+    mode: str = "none"
+    weights: Optional[Tuple[int, np.ndarray]] = None
+
+
+def gaussian_weights(sigma: float) -> Tuple[int, np.ndarray]:
+    """(radius, w) of scipy.ndimage.gaussian_filter for ``sigma`` (truncate 4.0): radius = int(4 sigma + 0.5), p[x] = exp(-0.5 / sigma^2 *
+    x^2) over x = -radius..radius in float64, w[j] = p[radius + j] / sum(p) (w[0] the centre weight).  sigma <= 1e-15 gives (-1, [1.0]):
+    scipy skips such a filter."""
+    sigma = float(sigma)
+    if not sigma > 1e-15:
+        return -1, np.ones(1, np.float64)
+    radius = int(4.0 * sigma + 0.5)
+    if radius > L.DISTORT_MAX_RADIUS:
+        raise ValueError(f"sigma {sigma} needs radius {radius} > {L.DISTORT_MAX_RADIUS}")
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return radius, phi[radius:].copy()
+
+
+def host_minsize(meta: Optional[PageMeta], crop: CropParams, width: int = 768, height: int = 768) -> np.float32:
+    """The ``minsize`` the device will return for this crop (include/ftc_sample.h: the minimum over the drawn glyphs of max(gw, gh), 0
+    when none is drawn), in the same fp32 operations.  The reference scales its salt and distortion by it."""
+    if crop.blank or meta is None or len(meta.position) == 0:
+        return f32(0)
+    boxes = forward_boxes(meta.position, crop.fwd)
+    cx, cy = boxes[:, 0] - f32(crop.startx), boxes[:, 1] - f32(crop.starty)
+    m = np.where(boxes[:, 3] > boxes[:, 2], boxes[:, 3], boxes[:, 2])
+    drawn = (cx > 0) & (cx < f32(width)) & (cy > 0) & (cy < f32(height)) & (m > 0)
+    return f32(m[drawn].min()) if drawn.any() else f32(0)
+
+
+def draw_salt_params(rng, minsize, width: int = 768, height: int = 768, prob: Optional[float] = None) -> Optional[SaltParams]:
+    """``random_salt`` and its call site in ``transforms3``: the ``< 0.2`` gate and ``prob = 0.2 * rng.random()`` (both skipped when
+    ``prob`` is given), ``rng.integers(1, 16)``, then ``rng.choice([0, 1, nan], p=[prob / 2, 1 - prob, prob / 2])`` over the block grid --
+    the same calls in the same order, so the grid equals the reference's for the same Generator state.  None: no salt."""
+    if prob is None:
+        if not rng.random() < 0.2:
+            return None
+        prob = 0.2 * rng.random()
+    s = min(max(1, int(float(minsize) / 4)), int(rng.integers(1, 16)))
+    shape = ((height + s) // s, (width + s) // s)
+    noise = np.asarray(rng.choice([0, 1, np.nan], p=[prob / 2, 1 - prob, prob / 2], size=shape), np.float64)
+    grid = np.where(np.isnan(noise), 2, np.where(noise == 0, 1, 0)).astype(np.uint8)
+    return SaltParams(int(s), grid)
+
+
+def draw_distort_params(rng, minsize) -> DistortParams:
+    """``random_distortion``: the ``< 0.3`` noise gate with alpha = min(0.4 u, 20 / max(1, s)); the ``< 0.3`` blur gate with sigma =
+    min(s / 8, 1.5 u); else the ``< 0.3`` sharpen gate with k = 10 u and sigma = 5.  Where the reference draws the normal field, one
+    64-bit seed is drawn (``rng.integers(0, 2**64, dtype=uint64)``): the field itself comes from the device (Philox4x32-10 + Box-Muller,
+    include/ftc_sample_aug.h).  The same Generator state gives the same parameters; numpy's ziggurat normal stream is not reproduced, so
+    later draws of a shared Generator differ from the reference's after a noise draw."""
+    s = float(minsize)
+    d = DistortParams()
+    if rng.random() < 0.3:
+        d.alpha = min(0.4 * rng.random(), 20 / max(1, s))
+        d.seed = int(rng.integers(0, 2 ** 64, dtype=np.uint64))
+    if rng.random() < 0.3:
+        d.mode, d.sigma = "blur", min(s / 8, 1.5 * rng.random())
+    elif rng.random() < 0.3:
+        d.mode, d.k, d.sigma = "sharpen", 10. * rng.random(), 5.
+    return d
+
+
+def draw_augment(rng, meta: Optional[PageMeta], crop: CropParams, kind: Optional[str] = None, bg_mean=None, bg_image=None, bg_offset=(0, 0),
+                 width: int = 768, height: int = 768):
+    """(salt, colour, distort) for one gray-variant sample in ``transforms3``'s order: the salt draws, the colouring's, the distortion's,
+    the last two scaled by ``host_minsize(meta, crop)``."""
+    ms = host_minsize(meta, crop, width, height)
+    salt = draw_salt_params(rng, ms, width, height)
+    colour = draw_colour_params(rng, kind, bg_mean, bg_image, bg_offset, width, height)
+    return salt, colour, draw_distort_params(rng, ms)
 
 
 def _uniform_of(rng: np.random.Generator) -> Callable[[], np.float32]:
@@ -346,12 +443,69 @@ def fill_desc(d: "L.SampleDesc", page: Optional[Page], crop: CropParams, colour:
         d.bg_y0, d.bg_x0 = int(colour.bg_offset[0]), int(colour.bg_offset[1])
 
 
+def _upload(table, device):
+    import torch
+    return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(device)
+
+
+def fill_salt_table(salt_params: Sequence[Optional[SaltParams]], device):
+    """The ftc_salt_desc table of include/ftc_sample_aug.h and the uploaded grids it points to (keep them until the call is made).  Codes
+    outside 0..2 are refused here: the library never reads a grid on the host."""
+    import torch
+    table = (L.SaltDesc * len(salt_params))()
+    keep = []
+    for d, sp in zip(table, salt_params):
+        if sp is None:
+            continue
+        grid = sp.grid
+        if isinstance(grid, torch.Tensor):
+            if not grid.is_cuda or not grid.is_contiguous() or grid.dtype != torch.uint8 or grid.dim() != 2:
+                raise ValueError("SaltParams.grid must be a contiguous uint8 [gh, gw] tensor on the GPU, or a NumPy array")
+        else:
+            grid = np.ascontiguousarray(grid)
+            if grid.ndim != 2 or grid.dtype != np.uint8 or grid.size == 0 or int(grid.max()) > 2:
+                raise ValueError("SaltParams.grid must be uint8 [gh, gw] with codes 0..2")
+            grid = torch.from_numpy(grid).to(device)
+        keep.append(grid)
+        d.grid, d.step, d.grid_h, d.grid_w = grid.data_ptr(), int(sp.step), int(grid.shape[0]), int(grid.shape[1])
+    return table, keep
+
+
+def fill_distort_desc(d: "L.DistortDesc", p: Optional[DistortParams], H: int, W: int) -> None:
+    """One ftc_distort_desc of include/ftc_sample_aug.h; the weights are computed here, in float64."""
+    if p is None:
+        return
+    if p.mode not in ("none", "blur", "sharpen"):
+        raise ValueError(f"unknown distortion mode {p.mode!r}")
+    flags = 0
+    if p.alpha is not None:
+        flags |= L.DISTORT_NOISE
+        d.alpha, d.seed = float(p.alpha), int(p.seed) & (2 ** 64 - 1)
+        if p.noise is not None:
+            n = p.noise
+            if not n.is_cuda or not n.is_contiguous() or str(n.dtype) != "torch.float32" or tuple(n.shape) != (3, H, W):
+                raise ValueError(f"DistortParams.noise must be a contiguous float32 [3, {H}, {W}] tensor on the GPU")
+            d.noise = n.data_ptr()
+    if p.mode != "none":
+        flags |= L.DISTORT_BLUR if p.mode == "blur" else L.DISTORT_SHARPEN
+        radius, w = p.weights if p.weights is not None else gaussian_weights(p.sigma)
+        if radius > L.DISTORT_MAX_RADIUS or len(w) < radius + 1:
+            raise ValueError(f"radius {radius} outside -1..{L.DISTORT_MAX_RADIUS}, or fewer than radius + 1 weights")
+        d.radius, d.k = int(radius), float(p.k)
+        for j in range(max(radius, 0) + 1):
+            d.w[j] = float(w[j])
+    d.flags = flags
+
+
 class SampleSynth:
     """``SampleSynth(width, height, scale)(pages, crop_params, colour_params)`` -> (image [B,3,H,W] fp32, labelmap [B,5,H/s,W/s] fp32,
     idmap [B,2,H/s,W/s] int32, minsize [B] fp32): fresh contiguous tensors on the current (or given) stream, ready for
     ``TrainStep.forward_backward(image, labelmap, idmap)``.  One descriptor table is uploaded and one library call enqueues the work;
     nothing synchronises.  ``pages[i]`` may be None for a blank sample; ``colour_params`` may be None (or hold None) for colour-variant
-    samples.  ``random_salt`` / ``random_distortion`` of the reference are not applied: they stay with the caller.  No CPU fallback."""
+    samples.  ``salt_params`` / ``distort_params`` (one entry or None per sample) apply the reference's ``random_salt`` before the
+    colouring and its ``random_distortion`` after it, on the same stream; with both None the call is the plain ``ftc_sample_synth``.
+    Salt needs the gray variant.  Distortion of a colour-variant sample is allowed: the reference has none, it is an extension with the
+    same arithmetic.  No CPU fallback."""
 
     def __init__(self, width: int = 768, height: int = 768, scale: int = 4, device=None):
         import torch
@@ -364,11 +518,12 @@ class SampleSynth:
         L.load()
 
     def __call__(self, pages: Sequence[Optional[Page]], crop_params: Sequence[CropParams], colour_params: Optional[Sequence[Optional[ColourParams]]] = None,
+                 salt_params: Optional[Sequence[Optional[SaltParams]]] = None, distort_params: Optional[Sequence[Optional[DistortParams]]] = None,
                  stream=None):
         import torch
         B = len(crop_params)
-        if B < 1 or len(pages) != B or (colour_params is not None and len(colour_params) != B):
-            raise ValueError("pages, crop_params and colour_params must have one entry per sample (B >= 1)")
+        if B < 1 or len(pages) != B or any(p is not None and len(p) != B for p in (colour_params, salt_params, distort_params)):
+            raise ValueError("pages, crop_params, colour_params, salt_params and distort_params must have one entry per sample (B >= 1)")
         table = (L.SampleDesc * B)()
         for b in range(B):
             fill_desc(table[b], pages[b], crop_params[b], None if colour_params is None else colour_params[b])
@@ -376,11 +531,62 @@ class SampleSynth:
         lib = L.load()
         with torch.cuda.device(self.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
             cur = torch.cuda.current_stream(self.device)
-            table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.device)
+            table_dev = _upload(table, self.device)
             image = torch.empty((B, 3, H, W), dtype=torch.float32, device=self.device)
             labelmap = torch.empty((B, 5, H // s, W // s), dtype=torch.float32, device=self.device)
             idmap = torch.empty((B, 2, H // s, W // s), dtype=torch.int32, device=self.device)
             minsize = torch.empty((B,), dtype=torch.float32, device=self.device)
-            L.check(lib.ftc_sample_synth(table, C.c_void_p(table_dev.data_ptr()), B, H, W, s, C.c_void_p(image.data_ptr()), C.c_void_p(labelmap.data_ptr()),
-                                         C.c_void_p(idmap.data_ptr()), C.c_void_p(minsize.data_ptr()), C.c_void_p(cur.cuda_stream)), "ftc_sample_synth")
+            outs = (C.c_void_p(image.data_ptr()), C.c_void_p(labelmap.data_ptr()), C.c_void_p(idmap.data_ptr()), C.c_void_p(minsize.data_ptr()),
+                    C.c_void_p(cur.cuda_stream))
+            if salt_params is None and distort_params is None:
+                L.check(lib.ftc_sample_synth(table, C.c_void_p(table_dev.data_ptr()), B, H, W, s, *outs), "ftc_sample_synth")
+                return image, labelmap, idmap, minsize
+            salt, keep = fill_salt_table(salt_params if salt_params is not None else [None] * B, self.device)
+            salt_dev = _upload(salt, self.device)
+            L.check(lib.ftc_sample_synth_salt(table, C.c_void_p(table_dev.data_ptr()), salt, C.c_void_p(salt_dev.data_ptr()), B, H, W, s, *outs),
+                    "ftc_sample_synth_salt")
+            if distort_params is not None:
+                self._distort(image, distort_params, cur)
         return image, labelmap, idmap, minsize
+
+    def _distort(self, image, distort_params, cur) -> None:
+        """ftc_sample_distort on `image` [B, 3, H, W], enqueued on `cur` (the current stream: the temporaries are allocated on it)."""
+        import torch
+        B, _, H, W = image.shape
+        table = (L.DistortDesc * B)()
+        for b in range(B):
+            fill_distort_desc(table[b], distort_params[b], H, W)
+        if not any(table[b].flags for b in range(B)):
+            return
+        lib = L.load()
+        need = int(lib.ftc_sample_distort_workspace_bytes(B, H, W))
+        if need < 0:
+            raise ValueError(f"distort: bad sizes B={B}, H={H}, W={W}")
+        table_dev = _upload(table, self.device)
+        workspace = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        L.check(lib.ftc_sample_distort(table, C.c_void_p(table_dev.data_ptr()), B, H, W, C.c_void_p(image.data_ptr()), C.c_void_p(workspace.data_ptr()),
+                                       need, C.c_void_p(cur.cuda_stream)), "ftc_sample_distort")
+
+    def distort(self, image, distort_params: Sequence[Optional[DistortParams]], stream=None):
+        """``random_distortion`` on an image the caller already has: ``image`` [B, 3, H, W] (or [3, H, W] with one DistortParams) fp32,
+        contiguous, on the GPU, any H and W; distorted IN PLACE and returned.  Nothing synchronises."""
+        import torch
+        if isinstance(distort_params, DistortParams) or distort_params is None:
+            distort_params = [distort_params]
+        if not image.is_cuda or not image.is_contiguous() or image.dtype != torch.float32 or image.dim() not in (3, 4) or image.shape[-3] != 3:
+            raise ValueError("image must be a contiguous float32 [B, 3, H, W] tensor on the GPU (there is no CPU fallback)")
+        batch = image if image.dim() == 4 else image.unsqueeze(0)
+        if len(distort_params) != batch.shape[0]:
+            raise ValueError("distort_params must have one entry per image")
+        with torch.cuda.device(self.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            self._distort(batch, distort_params, torch.cuda.current_stream(self.device))
+        return image
+
+    def normal_field(self, seed: int, n_elems: int, stream=None):
+        """The device's normal field of ``seed`` (ftc_sample_normal_fill): fp32 [n_elems], the values ``DistortParams(seed=...)`` adds."""
+        import torch
+        with torch.cuda.device(self.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            out = torch.empty((int(n_elems),), dtype=torch.float32, device=self.device)
+            L.check(L.load().ftc_sample_normal_fill(C.c_uint64(int(seed) & (2 ** 64 - 1)), int(n_elems), C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "ftc_sample_normal_fill")
+        return out

@@ -6,7 +6,8 @@
  * the versions of the other headers are not affected by it.
  *
  * All randomness stays with the caller: every draw of the reference arrives as a number in the descriptor, and the device work is a pure
- * function of (pages, descriptors).  The noise and blur of the reference's random_salt / random_distortion are not part of this surface.
+ * function of (pages, descriptors).  The noise and blur of the reference's random_salt / random_distortion are a surface of their own,
+ * ftc_sample_aug.h: ftc_sample_synth_salt there is this call with the salt applied to the gray crop, ftc_sample_distort follows it.
  *
  * Outputs for B samples, output size H x W, map scale s (h = H / s, w = W / s):
  *   image    [B][3][H][W] fp32      labelmap [B][5][h][w] fp32      idmap [B][2][h][w] int32      minsize [B] fp32

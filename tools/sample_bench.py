@@ -10,7 +10,14 @@ colourings, one nearest-neighbour sample).
            sample on one core -- a vectorised stand-in for the reference's per-pixel loops, not the reference itself -- and, for the first
            sample, the device result checked against it (image, rasters, ids, minsize bit for bit).
 
-    python tools/sample_bench.py [--batch 8] [--iters 20] [--repeats 5] [--warmup 3] [--oracle-samples 2] [--json PATH]
+  aug      (``--aug``) the augmentations of include/ftc_sample_aug.h at 768 x 768, B = 8 and 32: microseconds per image of the library call
+           alone (one table, one workspace, the image distorted in place over and over: the time does not depend on the values) for noise
+           only (seeded field), blur radius 6, sharpen radius 20, and of ``SampleSynth`` end to end with salt + noise + sharpen; each as
+           effective GB/s against the compulsory 14.16 MB per image (one read + one write).  Beside them the unaugmented call, and the
+           same distortion on the host for one image: scipy's ``gaussian_filter`` as the reference calls it, or tests/aug_oracle.py
+           where scipy is absent.
+
+    python tools/sample_bench.py [--batch 8] [--iters 20] [--repeats 5] [--warmup 3] [--oracle-samples 2] [--aug] [--json PATH]
 
 Prints one JSON line.  The figure to set the device time against is ``train_step.ms_per_step`` of ``bench.py`` on the same machine.
 """
@@ -62,6 +69,59 @@ def seeded_page(seed: int, h: int = 3000, w: int = 2000, n: int = 1500):
     return image, textline, sepline, position, codelist
 
 
+def host_distortion_ms(H: int, W: int) -> dict:
+    """noise + sharpen (sigma 5) on one [3, H, W] float32 image on the host, as random_distortion evaluates it."""
+    import aug_oracle as ao
+    rng = np.random.Generator(np.random.PCG64(5))
+    im = rng.random((3, H, W)).astype(np.float32)
+    try:
+        from scipy.ndimage import gaussian_filter
+        blur, how = (lambda x: gaussian_filter(x, sigma=5.)), "scipy.ndimage.gaussian_filter"
+    except ImportError:
+        r, w = ao.gaussian_weights(5.0)
+        blur, how = (lambda x: ao.gaussian(x, r, w)), "tests/aug_oracle.py"
+    times = []
+    for _ in range(3):
+        t = time.perf_counter()
+        x = im.copy()
+        x += 0.2 * rng.normal(size=x.shape)
+        x = np.clip(x, 0, 1)
+        x = np.clip(x + 8.0 * (x - blur(x)), 0, 1)
+        times.append(time.perf_counter() - t)
+    return {"how": how, "noise_sharpen_ms_per_image": statistics.median(times) * 1e3}
+
+
+def aug_section(events, synth, pages, crops, colours, H: int, W: int) -> dict:
+    lib = L.load()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    mb = 2 * 3 * H * W * 4 / 1e6
+    out = {"compulsory_mb_per_image": mb, "host": host_distortion_ms(H, W)}
+    kinds = {"noise": S.DistortParams(alpha=0.2, seed=1), "blur_r6": S.DistortParams(mode="blur", sigma=1.5),
+             "sharpen_r20": S.DistortParams(mode="sharpen", sigma=5.0, k=8.0), "noise_sharpen_r20": S.DistortParams(alpha=0.2, seed=1, mode="sharpen", sigma=5.0, k=8.0)}
+    for B in (8, 32):
+        image = torch.rand((B, 3, H, W), device="cuda")
+        need = int(lib.ftc_sample_distort_workspace_bytes(B, H, W))
+        ws = torch.empty((need,), dtype=torch.uint8, device="cuda")
+        for name, p in kinds.items():
+            table = (L.DistortDesc * B)()
+            for b in range(B):
+                S.fill_distort_desc(table[b], p, H, W)
+            dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).cuda()
+            r = events(lambda: L.check(lib.ftc_sample_distort(table, C.c_void_p(dev.data_ptr()), B, H, W, C.c_void_p(image.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                                              need, stream), "ftc_sample_distort"))
+            us = r["ms_per_batch_median"] * 1e3 / B
+            out[f"{name}_B{B}"] = {"us_per_image": us, "effective_gb_s": mb * 1e-3 / (us * 1e-6), "spread": r["spread"]}
+        n = len(crops)
+        pick = lambda seq: [seq[b % n] for b in range(B)]      # noqa: E731
+        salt = [S.SaltParams(4, np.random.Generator(np.random.PCG64(b)).integers(0, 3, ((H + 4) // 4, (W + 4) // 4), dtype=np.uint8)) for b in range(B)]
+        salt_dev = [S.SaltParams(sp.step, torch.from_numpy(sp.grid).cuda()) for sp in salt]
+        for name, kw in (("synth_plain", {}), ("synth_salt_noise_sharpen", dict(salt_params=salt_dev, distort_params=[kinds["noise_sharpen_r20"]] * B))):
+            r = events(lambda: synth(pick(pages), pick(crops), pick(colours), **kw))
+            us = r["ms_per_batch_median"] * 1e3 / B
+            out[f"{name}_B{B}"] = {"us_per_image": us, "effective_gb_s": mb * 1e-3 / (us * 1e-6), "spread": r["spread"]}
+    return out
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -69,6 +129,7 @@ def main() -> None:
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--oracle-samples", type=int, default=2)
+    ap.add_argument("--aug", action="store_true", help="also time the augmentations of include/ftc_sample_aug.h")
     ap.add_argument("--json", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -138,6 +199,8 @@ def main() -> None:
               "glyphs_per_page": len(arrays[0][3]), "glyphs_drawn": drawn, "size_x": [round(c.record["size_x"], 3) for c in crops],
               "iters": a.iters, "repeats": a.repeats, "synth_call": call, "kernels_only": kern,
               "oracle_ms_per_sample": statistics.median(host_s) * 1e3 if host_s else None, "oracle_samples": len(host_s), "checked_against_oracle": bool(host_s)}
+    if a.aug:
+        result["aug"] = aug_section(events, synth, pages, crops, colours, H, W)
     line = json.dumps(result)
     print(line)
     if a.json:
