@@ -306,14 +306,10 @@ const char* validate_op(const ftc_op& o, const ftc_plan* pl, std::string* why) {
         return nullptr;
     }
     case FTC_OP_WGRAD: {
-        if (o.Cin <= 0 || o.Cout <= 0 || o.Ho <= 0 || o.Wo <= 0 || (o.ksize != 1 && o.ksize != 3) || (o.stride != 1 && o.stride != 2)) return "wgrad: bad sizes";
-        if (o.w_dtype != FTC_F32 && !ftc_is16(o.w_dtype)) return "wgrad: unknown compute type";
-        if ((o.in_dtype != FTC_F32 && o.in_dtype != o.w_dtype) || (o.res_dtype != FTC_F32 && o.res_dtype != o.w_dtype))
-            return "wgrad: operands are fp32 or 16-bit copies in the compute type (in_dtype: layer input, res_dtype: output gradient)";
-        const int pad = (o.ksize - 1) / 2;
-        if (o.Ho != (o.H + 2 * pad - o.ksize) / o.stride + 1 || o.Wo != (o.W + 2 * pad - o.ksize) / o.stride + 1) return "wgrad: Ho/Wo inconsistent";
+        // the op's form and its kernel choice (wgrad_choice.h) come first, as the form checks always did: a malformed op reports its form, not a missing buffer
+        wgradimpl::WgradChoice wc;
+        if (const char* refused = wgradimpl::wgrad_resolve(o, &wc)) return refused;
         const int64_t cit = o.Cin_total > 0 ? o.Cin_total : o.Cin, cot = o.Cout_total > 0 ? o.Cout_total : o.Cout;
-        if (o.cin_off + o.Cin > cit || o.cout_off + o.Cout > cot || o.aux0 < 1 || o.aux0 > 4096) return "wgrad: channel slices / splits out of range";
         const int64_t kk = (int64_t)o.ksize * o.ksize;
         if (!need(o.in, true, "in", pin * cit * es(o.in_dtype)) || !need(o.in2, true, "in2", pout * cot * es(o.res_dtype)) || !need(o.out, true, "out", kk * o.Cout * o.Cin * 4) ||
             !need(o.aux, true, "aux", (int64_t)o.aux0 * kk * o.Cout * o.Cin * 4) || !need(o.scale, (o.flags & FTC_FLAG_SE_SCALE) != 0, "scale", (int64_t)o.B * o.Cin * 4)) return why->c_str();
@@ -578,7 +574,7 @@ int ftc_op_kernel_label(const ftc_op* op, char* buf, int len) {
     case FTC_OP_LOSS_BWD: std::snprintf(buf, len, "maploss_bwd+idloss_bwd"); break;
     case FTC_OP_SCATTER_ROWS: std::snprintf(buf, len, "scatter_rows_kernel"); break;
     case FTC_OP_BNBWD: std::snprintf(buf, len, "bnbwd_partial+final+apply"); break;
-    case FTC_OP_WGRAD: std::snprintf(buf, len, "wgrad_kernel<%s,k%d,s%d>+reduce", ftc_dtname(op->w_dtype), op->ksize, op->stride); break;
+    case FTC_OP_WGRAD: wgrad_kernel_label(*op, buf, len); break;
     case FTC_OP_DWBWD: std::snprintf(buf, len, "dwbwd_data+weight<s%d>", op->stride); break;
     case FTC_OP_SEBWD: std::snprintf(buf, len, "sebwd_ds+mlp+w"); break;
     case FTC_OP_UPCATBWD: std::snprintf(buf, len, "upcatbwd_kernel"); break;

@@ -8,6 +8,7 @@
 
 #include "../../include/ftc.h"
 #include "conv_choice.h"
+#include "wgrad_choice.h"
 
 struct ftc_plan {
     std::vector<ftc_op> ops;
@@ -30,6 +31,9 @@ bool ftc_fmbconv_legal(const ftc_op& o);
 // conv_igemm.hip: NULL if the convolution op (incl. its tuned kernel choice ftc_op.aux0) is supported, else the reason
 // (conv_choice.h: the choice itself, and conv_pinned_choice / conv_small_tile_choice, which write one back into aux0)
 const char* conv_validate(const ftc_op& op);
+
+// wgrad.hip: the kernel label of an FTC_OP_WGRAD op (wgrad_choice.h: wgrad_resolve + wgrad_format_label)
+void wgrad_kernel_label(const ftc_op& op, char* buf, int len);
 
 // ftc_api.hip: opt-in of `kernel` to `bytes` (> 64 KB) of dynamic LDS, made once per (kernel, device): looks up the calling thread's
 // current device, so it holds when that changes and when host threads race on a first launch; afterwards its only HIP call is hipGetDevice.

@@ -13,6 +13,8 @@
 #include "ftc_common.h"
 #include "ftc_host.h"
 
+using namespace wgradimpl;
+
 namespace {
 
 template <typename WT> struct WFrag;
@@ -817,10 +819,6 @@ __global__ __launch_bounds__(256) void wgrad_thin_kernel(WgradP p) {
         }
 }
 
-inline bool wgrad_thin_shape(int Cout, int Cin, int ksize, int stride) { return Cout <= 2 && stride == 1 && (ksize == 3 || ksize == 1) && Cin % 8 == 0 && Cin <= 1024; }
-
-inline bool wgrad3_shape(int Wo, int Cout, int Cin, int ksize) { return ksize == 3 && Wo % 32 == 0 && Cout >= 32 && Cin >= 32; }
-
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int S, int KK, int Cout, int Cin) {
     const long per = (long)KK * Cout * Cin;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long)gridDim.x * 256) {
@@ -854,134 +852,109 @@ __global__ __launch_bounds__(256) void wgrad_reduce_wide_kernel(const float* __r
     out[((long)co * Cin + ci) * KK + tap] += s;
 }
 
-inline hipError_t launch_wgrad_reduce(const void* part, float* out, int S, int KK, int Cout, int Cin, hipStream_t s) {
-    const long per = (long)KK * Cout * Cin;
-    if (S >= 48) {
-        hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((per + 15) / 16)), dim3(256), 0, s, (const float*)part, out, S, KK, Cout, Cin);
+// The launchers below take the WgradChoice of wgrad_resolve (wgrad_choice.h) and decide nothing from the ftc_op.  One that has no instantiation for the
+// choice it is handed returns hipErrorInvalidValue: wgrad_resolve refuses such ops at plan creation, so these returns are unreachable -- keep it that way.
+inline dim3 wg_grid(const WgradChoice& c) { return dim3(c.grid[0], c.grid[1], c.grid[2]); }
+
+inline hipError_t launch_wgrad_reduce(const WgradP& p, float* out, const WgradChoice& c, hipStream_t s) {
+    const long per = (long)c.KK * p.Cout * p.Cin;
+    if (c.reduce_wide) {
+        hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3((unsigned)((per + 15) / 16)), dim3(256), 0, s, (const float*)p.part, out, c.splits, c.KK, p.Cout, p.Cin);
     } else {
         const long nb = (per + 255) / 256;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(nb > 8192 ? 8192 : nb)), dim3(256), 0, s, (const float*)part, out, S, KK, Cout, Cin);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(nb > 8192 ? 8192 : nb)), dim3(256), 0, s, (const float*)p.part, out, c.splits, c.KK, p.Cout, p.Cin);
     }
     return hipGetLastError();
 }
 
-struct WgCfg { int id, BM, BN; };
-inline WgCfg wgrad_cfg(int Cout, int Cin, int ksize) {
-    if (Cout <= 32) return {0, 32, 128};
-    if (Cout <= 64 || Cin <= 64) return {1, 64, 64};
-    // every (Cout tile, Cin tile, tap) workgroup re-reads its two operand streams: the kernel is bound by those re-reads (last FPN level:
-    // 4.7 GB per launch at 128 x 128), so wide layers take the 192 x 256 tile (12 accumulators per wave, one workgroup per CU)
-    if (ksize == 3 && Cout >= 192 && Cin >= 256) return {3, 192, 256};        // (1x1 layers: measured slower, 25.5 -> 29.6 ms per step)
-    return {2, 128, 128};
+template <typename XT>
+hipError_t launch_thin(const WgradP& p, const WgradChoice& c, hipStream_t s) {
+    const int form = c.thin_ks * 10 + c.thin_co;
+    if (form == 31) hipLaunchKernelGGL((wgrad_thin_kernel<XT, 1, 3>), wg_grid(c), dim3(256), 0, s, p);
+    else if (form == 32) hipLaunchKernelGGL((wgrad_thin_kernel<XT, 2, 3>), wg_grid(c), dim3(256), 0, s, p);
+    else if (form == 11) hipLaunchKernelGGL((wgrad_thin_kernel<XT, 1, 1>), wg_grid(c), dim3(256), 0, s, p);
+    else if (form == 12) hipLaunchKernelGGL((wgrad_thin_kernel<XT, 2, 1>), wg_grid(c), dim3(256), 0, s, p);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
 }
 
+template <typename WT>
+hipError_t launch_nine(const WgradP& p, const WgradChoice& c, hipStream_t s) {
+    if (c.family == WGRAD_NINE_TR) hipLaunchKernelGGL(wgrad3t_kernel<WT>, wg_grid(c), dim3(256), 0, s, p, c.nseg, c.steps_per_split);
+    else hipLaunchKernelGGL(wgrad3_kernel<WT>, wg_grid(c), dim3(256), 0, s, p, c.nseg, c.steps_per_split);
+    return hipGetLastError();
+}
+
+template <typename WT>
+hipError_t launch_ring(const WgradP& p, const WgradChoice& c, hipStream_t s) {
+    const hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(wgrad1t_kernel<WT>), c.lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(wgrad1t_kernel<WT>, wg_grid(c), dim3(256), (size_t)c.lds_bytes, s, p);
+    return hipGetLastError();
+}
+
+// XT / DT: storage of the layer input / of the output gradient (fp32, or a 16-bit copy in the compute type)
 template <typename WT, typename XT, typename DT>
-void launch_cfg(const WgradP& p, int cfg, dim3 grid, hipStream_t s) {
-    if (cfg == 0) hipLaunchKernelGGL((wgrad_kernel<WT, XT, DT, 1, 1, 1, 4>), grid, dim3(256), 0, s, p);
-    else if (cfg == 1) hipLaunchKernelGGL((wgrad_kernel<WT, XT, DT, 1, 1, 2, 2>), grid, dim3(256), 0, s, p);
-    else if (cfg == 3) hipLaunchKernelGGL((wgrad_kernel<WT, XT, DT, 3, 4, 2, 2>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((wgrad_kernel<WT, XT, DT, 2, 2, 2, 2>), grid, dim3(256), 0, s, p);
+hipError_t launch_tile(const WgradP& p, const WgradChoice& c, hipStream_t s) {
+    switch (c.tile) {
+    case WG_TILE_32x128: hipLaunchKernelGGL((wgrad_kernel<WT, XT, DT, 1, 1, 1, 4>), wg_grid(c), dim3(256), 0, s, p); break;
+    case WG_TILE_64x64: hipLaunchKernelGGL((wgrad_kernel<WT, XT, DT, 1, 1, 2, 2>), wg_grid(c), dim3(256), 0, s, p); break;
+    case WG_TILE_128x128: hipLaunchKernelGGL((wgrad_kernel<WT, XT, DT, 2, 2, 2, 2>), wg_grid(c), dim3(256), 0, s, p); break;
+    case WG_TILE_192x256: hipLaunchKernelGGL((wgrad_kernel<WT, XT, DT, 3, 4, 2, 2>), wg_grid(c), dim3(256), 0, s, p); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 // 16-bit compute type: every combination of fp32 / 16-bit storage of the two operands
 template <typename WT>
-void launch_io(const WgradP& p, int cfg, dim3 grid, bool x16, bool d16, hipStream_t s) {
-    if (x16 && d16) launch_cfg<WT, WT, WT>(p, cfg, grid, s);
-    else if (x16) launch_cfg<WT, WT, float>(p, cfg, grid, s);
-    else if (d16) launch_cfg<WT, float, WT>(p, cfg, grid, s);
-    else launch_cfg<WT, float, float>(p, cfg, grid, s);
+hipError_t launch_generic16(const WgradP& p, const WgradChoice& c, hipStream_t s) {
+    const bool x16 = c.x_dtype == c.w_dtype, d16 = c.dz_dtype == c.w_dtype;
+    if ((!x16 && c.x_dtype != FTC_F32) || (!d16 && c.dz_dtype != FTC_F32)) return hipErrorInvalidValue;
+    if (x16 && d16) return launch_tile<WT, WT, WT>(p, c, s);
+    if (x16) return launch_tile<WT, WT, float>(p, c, s);
+    if (d16) return launch_tile<WT, float, WT>(p, c, s);
+    return launch_tile<WT, float, float>(p, c, s);
 }
 
 }  // namespace
 
-int ftc_wgrad_splits_impl(int B, int Ho, int Wo, int Cout, int Cin, int ksize) {
-    const WgCfg c = wgrad_cfg(Cout, Cin, ksize);
-    long tiles = (long)((Cout + c.BM - 1) / c.BM) * ((Cin + c.BN - 1) / c.BN) * ksize * ksize;
-    if (wgrad3_shape(Wo, Cout, Cin, ksize)) tiles = (long)((Cout + 63) / 64) * ((Cin + 63) / 64);      // the nine-tap kernel: 64 x 64 tiles, taps inside
-    const long P = (long)B * Ho * Wo;
-    if (wgrad_thin_shape(Cout, Cin, ksize, 1)) {                  // (the thin kernel: one workgroup per ~1024 pixels, at most 512)
-        const long st = (P + 1023) / 1024;
-        return (int)(st < 1 ? 1 : st > 512 ? 512 : st);
-    }
-    long S = (1536 + tiles - 1) / tiles;                          // ~6 workgroups per CU in flight
-    // ... but every split writes (and the reduction re-reads) a full fp32 copy of the gradient: on the deep stages (4608 pixels, 1.5 M
-    // weights) 16 splits moved 200 MB of partial sums around 33 MB of operands.  At least 1024 pixels (16 K steps) per split.
-    const long smax = (P + 1023) / 1024;
-    if (S > smax) S = smax;
-    if (S < 1) S = 1;
-    if (S > 4096) S = 4096;
-    return (int)S;
+int ftc_wgrad_splits_impl(int B, int Ho, int Wo, int Cout, int Cin, int ksize) { return wgrad_splits(B, Ho, Wo, Cout, Cin, ksize); }
+
+void wgrad_kernel_label(const ftc_op& op, char* buf, int len) {
+    WgradChoice c;
+    if (wgrad_resolve(op, &c) != nullptr) std::snprintf(buf, len, "wgrad<refused>");
+    else wgrad_format_label(op, c, buf, len);
 }
 
 hipError_t launch_wgrad(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
+    WgradChoice c;
+    if (wgrad_resolve(o, &c) != nullptr) return hipErrorInvalidValue;      // (plan creation refuses such ops)
     WgradP p;
-    p.x = a.in; p.dz = a.in2; p.se = (o.flags & FTC_FLAG_SE_SCALE) ? a.scale : nullptr; p.part = a.aux;
+    p.x = a.in; p.dz = a.in2; p.se = c.gated ? a.scale : nullptr; p.part = a.aux;
     p.B = o.B; p.H = o.H; p.W = o.W; p.Ho = o.Ho; p.Wo = o.Wo;
     p.Cin = o.Cin; p.CinT = o.Cin_total > 0 ? o.Cin_total : o.Cin; p.cin_off = o.cin_off;
     p.Cout = o.Cout; p.CoutT = o.Cout_total > 0 ? o.Cout_total : o.Cout; p.cout_off = o.cout_off;
     p.KS = o.ksize; p.stride = o.stride; p.pad = (o.ksize - 1) / 2;
     p.P = (long)o.B * o.Ho * o.Wo;
-    const int S = o.aux0 > 0 ? o.aux0 : 1;
-    const int BK = o.w_dtype == FTC_F32 ? 32 : 64;
-    p.chunk = ((p.P + S - 1) / S + BK - 1) / BK * BK;
-    const long HoWo = (long)o.Ho * o.Wo;
-    p.se_epi = (p.se && o.ksize == 1 && o.stride == 1 && HoWo % p.chunk == 0) ? 1 : 0;
-    const int KK = o.ksize * o.ksize;
-    if (wgrad_thin_shape(o.Cout, o.Cin, o.ksize, o.stride) && o.res_dtype == FTC_F32 && !p.se && o.H == o.Ho && o.W == o.Wo && !(o.flags & 0x100) &&
-        p.CinT % 8 == 0 && p.cin_off % 8 == 0) {
-        p.chunk = (p.P + S - 1) / S;
-#define THIN(XT) do { if (o.ksize == 3) { if (o.Cout == 1) hipLaunchKernelGGL((wgrad_thin_kernel<XT, 1, 3>), dim3(S), dim3(256), 0, s, p); \
-                                           else hipLaunchKernelGGL((wgrad_thin_kernel<XT, 2, 3>), dim3(S), dim3(256), 0, s, p); } \
-                      else { if (o.Cout == 1) hipLaunchKernelGGL((wgrad_thin_kernel<XT, 1, 1>), dim3(S), dim3(256), 0, s, p); \
-                             else hipLaunchKernelGGL((wgrad_thin_kernel<XT, 2, 1>), dim3(S), dim3(256), 0, s, p); } } while (0)
-        if (o.in_dtype == FTC_F32) THIN(float); else if (o.in_dtype == FTC_F16) THIN(_Float16); else THIN(__bf16);
-#undef THIN
-        hipError_t et = hipGetLastError();
-        if (et != hipSuccess) return et;
-        return launch_wgrad_reduce(a.aux, (float*)a.out, S, KK, o.Cout, o.Cin, s);
+    p.chunk = c.chunk;
+    p.se_epi = c.se_epi;
+    // the family's kernel in the types the choice names (the nine-tap and ring kernels exist for the two 16-bit types only)
+    const bool f16 = c.w_dtype == FTC_F16, bf16 = c.w_dtype == FTC_BF16;
+    hipError_t e = hipErrorInvalidValue;
+    switch (c.family) {
+    case WGRAD_THIN:
+        if (c.dz_dtype != FTC_F32) break;
+        e = c.x_dtype == FTC_F32 ? launch_thin<float>(p, c, s) : c.x_dtype == FTC_F16 ? launch_thin<_Float16>(p, c, s) : c.x_dtype == FTC_BF16 ? launch_thin<__bf16>(p, c, s) : e;
+        break;
+    case WGRAD_NINE_TR:
+    case WGRAD_NINE_STAGED: e = f16 ? launch_nine<_Float16>(p, c, s) : bf16 ? launch_nine<__bf16>(p, c, s) : e; break;
+    case WGRAD_RING: e = f16 ? launch_ring<_Float16>(p, c, s) : bf16 ? launch_ring<__bf16>(p, c, s) : e; break;
+    case WGRAD_GENERIC:
+        if (c.w_dtype == FTC_F32) e = c.x_dtype == FTC_F32 && c.dz_dtype == FTC_F32 ? launch_tile<float, float, float>(p, c, s) : e;
+        else e = f16 ? launch_generic16<_Float16>(p, c, s) : bf16 ? launch_generic16<__bf16>(p, c, s) : e;
+        break;
     }
-    if (wgrad3_shape(o.Wo, o.Cout, o.Cin, o.ksize) && o.stride == 1 && ftc_is16(o.w_dtype) && o.in_dtype == o.w_dtype && o.res_dtype == o.w_dtype && !p.se &&
-        !(o.flags & 0x100)) {                                    // (0x100: the generic kernel, for A/B measurements)
-        const int nseg = o.Wo / 32;
-        const long total = (long)o.B * nseg * o.Ho;
-        const long sps = (total + S - 1) / S;
-        const dim3 g3((o.Cout + 63) / 64, (o.Cin + 63) / 64, S);
-        // everything 8-channel (16-byte) aligned: the transpose-read kernel; 0x200 forces the staged one (A/B measurements, tests)
-        const bool al8 = o.Cout % 8 == 0 && o.Cin % 8 == 0 && p.CoutT % 8 == 0 && p.CinT % 8 == 0 && p.cout_off % 8 == 0 && p.cin_off % 8 == 0 && !(o.flags & 0x200);
-        if (al8 && o.w_dtype == FTC_F16) hipLaunchKernelGGL(wgrad3t_kernel<_Float16>, g3, dim3(256), 0, s, p, nseg, sps);
-        else if (al8) hipLaunchKernelGGL(wgrad3t_kernel<__bf16>, g3, dim3(256), 0, s, p, nseg, sps);
-        else if (o.w_dtype == FTC_F16) hipLaunchKernelGGL(wgrad3_kernel<_Float16>, g3, dim3(256), 0, s, p, nseg, sps);
-        else hipLaunchKernelGGL(wgrad3_kernel<__bf16>, g3, dim3(256), 0, s, p, nseg, sps);
-        hipError_t e3 = hipGetLastError();
-        if (e3 != hipSuccess) return e3;
-        return launch_wgrad_reduce(a.aux, (float*)a.out, S, KK, o.Cout, o.Cin, s);
-    }
-    // 1x1 stride 1, 16-bit copies of both operands, 8-channel aligned, no per-element gate: the DMA-ring kernel (0x200: the generic one)
-    if (o.ksize == 1 && o.stride == 1 && ftc_is16(o.w_dtype) && o.in_dtype == o.w_dtype && o.res_dtype == o.w_dtype && (!p.se || p.se_epi) && !(o.flags & 0x300) &&
-        o.Cout % 8 == 0 && o.Cin % 8 == 0 && p.CoutT % 8 == 0 && p.CinT % 8 == 0 && p.cout_off % 8 == 0 && p.cin_off % 8 == 0 && o.Cout >= 64 && o.Cin >= 64 &&
-        p.P * p.CoutT * 2 < 0x7fffffffL && p.P * p.CinT * 2 < 0x7fffffffL && p.chunk % 32 == 0) {
-        const dim3 g1((o.Cout + 127) / 128, (o.Cin + 127) / 128, S);
-        const size_t lds = (size_t)4 * 32 * 256 * 2;
-        if (o.w_dtype == FTC_F16) {
-            (void)ftc_allow_dyn_lds(reinterpret_cast<const void*>(wgrad1t_kernel<_Float16>), (int)lds);
-            hipLaunchKernelGGL(wgrad1t_kernel<_Float16>, g1, dim3(256), lds, s, p);
-        } else {
-            (void)ftc_allow_dyn_lds(reinterpret_cast<const void*>(wgrad1t_kernel<__bf16>), (int)lds);
-            hipLaunchKernelGGL(wgrad1t_kernel<__bf16>, g1, dim3(256), lds, s, p);
-        }
-        hipError_t e1 = hipGetLastError();
-        if (e1 != hipSuccess) return e1;
-        return launch_wgrad_reduce(a.aux, (float*)a.out, S, 1, o.Cout, o.Cin, s);
-    }
-    WgCfg c = wgrad_cfg(o.Cout, o.Cin, o.ksize);
-    // the 192 x 256 tile has one staging task per thread only with 16-byte accesses of 8 channels (16-bit copies) or the fp32 K step of 32
-    if (c.id == 3 && ftc_is16(o.w_dtype) && !(o.in_dtype == o.w_dtype && o.res_dtype == o.w_dtype)) c = WgCfg{2, 128, 128};
-    const dim3 grid((o.Cout + c.BM - 1) / c.BM, ((o.Cin + c.BN - 1) / c.BN) * KK, S);
-    // in_dtype / res_dtype: storage of the layer input / of the output gradient (fp32, or a 16-bit copy in the compute type)
-    if (o.w_dtype == FTC_F32) launch_cfg<float, float, float>(p, c.id, grid, s);
-    else if (o.w_dtype == FTC_F16) launch_io<_Float16>(p, c.id, grid, o.in_dtype == FTC_F16, o.res_dtype == FTC_F16, s);
-    else launch_io<__bf16>(p, c.id, grid, o.in_dtype == FTC_BF16, o.res_dtype == FTC_BF16, s);
-    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    return launch_wgrad_reduce(a.aux, (float*)a.out, S, KK, o.Cout, o.Cin, s);
+    return launch_wgrad_reduce(p, (float*)a.out, c, s);
 }

@@ -482,6 +482,113 @@ def test_conv_choice_header_is_host_only_and_clean_under_sanitizers(tmp_path):
         assert lab == gold["labels"][li] and (why == "" if ei < 0 else gold["errors"][ei].endswith(why) and why != ""), (line, gold["labels"][li], ei)
 
 
+# ---- the kernel choice of FTC_OP_WGRAD (csrc/wgrad_choice.h) ----------------------------------------------------------------------
+
+def test_wgrad_splits_match_the_recorded_ones():
+    """ftc_wgrad_splits over the shape grid of tests/wgrad_choice_sweep.py against tests/golden/wgrad_choices.json.gz (part "splits", written from the commit
+    before the rule moved next to wgrad_resolve)."""
+    import wgrad_choice_sweep as S
+    want = S.load_golden()["splits"]
+    got = S.replay_splits()
+    assert len(got) == len(want) == len(S.SPLIT_GRID)
+    bad = [(g, a, b) for g, a, b in zip(S.SPLIT_GRID, got, want) if a != b]
+    assert not bad, (len(bad), bad[:5])
+
+
+def test_wgrad_ops_of_the_train_plans_match_the_recorded_ones():
+    """Every field (aux0 = the split count and the buffer references included) of every FTC_OP_WGRAD op of the six train plans."""
+    import wgrad_choice_sweep as S
+    want = S.load_golden()["train_ops"]
+    got = S.train_ops()
+    assert sorted(got) == sorted(want)
+    for case in want:
+        assert len(got[case]) == len(want[case]) == 251, case
+        for i, (a, b) in enumerate(zip(got[case], want[case])):
+            assert a == b, (case, i, dict(zip(S.INT_FIELDS, a)), dict(zip(S.INT_FIELDS, b)))
+
+
+@pytest.mark.parametrize("part", ["cases", "train", "grid", "refused"])
+def test_wgrad_choice_sweep_matches_the_recorded_one(part):
+    """Which ops ftc_plan_create accepts, the full error text of the others and every kernel label, entry by entry against part "choices" of
+    tests/golden/wgrad_choices.json.gz (written when the conditions of launch_wgrad had moved into wgrad_resolve verbatim and nothing else had changed)."""
+    import wgrad_choice_sweep as S
+    gold = S.load_golden()
+    want = gold["choices"][part]
+    ents = S.entries(part)
+    got = S.replay_choices(part)
+    assert len(got) == len(want) == len(ents)
+    for i, ((lab, err), (li, ei)) in enumerate(zip(got, want)):
+        assert err == (None if ei < 0 else gold["errors"][ei]), (part, i, ents[i])
+        assert err is not None or lab == gold["labels"][li], (part, i, ents[i])          # (a refused op has no choice to label)
+    assert sum(err is None for _, err in got) == (0 if part == "refused" else len(want))
+
+
+def test_wgrad_cases_reach_every_kernel_family():
+    """The ops test_wgrad and test_wgrad_exact run (WG_CASES x the seven storage configurations, the row's own flags) reach, by their labels: all five
+    kernel families, both 16-bit types of the three 16-bit-only ones, the four tiles of the generic kernel, the thin kernel with 1 and 2 output channels at
+    k = 1 and k = 3, an SE gate applied while staging and one applied to the partial tile (generic kernel and DMA ring)."""
+    import wgrad_choice_sweep as S
+    from test_gpu_bwd_ops import WG_CASES
+    labels = set()
+    for c in WG_CASES:
+        for wd, io in S.STORAGE:
+            lab, err = S.verdict(S.make_op(S.case_fields(c, wd, io, S.case_flags(c))))
+            assert err is None, (c[0], wd, io, err)
+            labels.add(lab)
+    want = [f"{k}<{t}" for k in ("wgrad3t_kernel", "wgrad3_kernel", "wgrad1t_kernel") for t in ("bf16>", "f16>")]
+    want += ["wgrad1t_kernel<bf16,gate=epi>", "wgrad1t_kernel<f16,gate=epi>", "wgrad_kernel<f32,", "wgrad_kernel<bf16,", "wgrad_kernel<f16,", ",gate=staged>", ",gate=epi>"]
+    want += [f",tile={t}," for t in ("32x128", "64x64", "128x128", "192x256")]
+    want += [f",co={co},k={k}>" for co in (1, 2) for k in (1, 3)] + ["wgrad_thin_kernel<x=f32,", "wgrad_thin_kernel<x=bf16,"]
+    want += [f"wgrad_kernel<{w},x={x},dz={d}," for w, x, d in (("f32", "f32", "f32"), ("bf16", "f32", "f32"), ("bf16", "bf16", "f32"), ("bf16", "bf16", "bf16"), ("f16", "f32", "f16"))]
+    missing = [w for w in want if not any(w in lab and lab.endswith(("+reduce", "+reduce_wide")) for lab in labels)]
+    assert not missing, (missing, sorted(labels))
+
+
+@pytest.fixture(scope="module")
+def wgrad_choice_host(tmp_path_factory):
+    """tests/c_abi/wgrad_choice_host.cc (plain C++ over csrc/wgrad_choice.h alone, its own main) built with AddressSanitizer + UBSan; returns a function
+    that runs it on request lines and returns its output lines."""
+    import subprocess
+    exe = str(tmp_path_factory.mktemp("wgrad_choice") / "wgrad_choice_host")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "c_abi", "wgrad_choice_host.cc"), "-o", exe], check=True)
+
+    def run(lines):
+        r = subprocess.run([exe], input="".join(l + "\n" for l in lines), capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return r.stdout.split("\n")[:-1]
+    return run
+
+
+def test_wgrad_choice_header_is_host_only_and_clean_under_sanitizers(wgrad_choice_host):
+    """csrc/wgrad_choice.h needs no HIP header: the stand-alone program resolves and labels every op of the recorded sweeps and answers the recorded
+    split counts, what the library answered for the same entries."""
+    import wgrad_choice_sweep as S
+    gold = S.load_golden()
+    assert [int(v) for v in wgrad_choice_host(["s " + " ".join(map(str, g)) for g in S.SPLIT_GRID])] == gold["splits"]
+    for part in S.CHOICE_PARTS:
+        ents = S.entries(part)
+        lines = wgrad_choice_host(["o " + " ".join(str(int(f.get(n, 0))) for n in S.INT_FIELDS) for f in ents])
+        want = gold["choices"][part]
+        assert len(lines) == len(want)
+        for f, line, (li, ei) in zip(ents, lines, want):
+            why, lab = line.split("\t")[:2]
+            assert (why == "" and lab == gold["labels"][li]) if ei < 0 else (why != "" and gold["errors"][ei].endswith(why)), (part, f, line)
+
+
+def test_wgrad_labels_and_choices_correspond_one_to_one(wgrad_choice_host):
+    """Over the recorded sweeps: two ops with one label run one instantiation (family, template arguments, form of the gate, reduction kernel), and two
+    ops that run one instantiation have one label."""
+    import wgrad_choice_sweep as S
+    by_label, by_choice = {}, {}
+    for part in ("cases", "train", "grid"):
+        for line in wgrad_choice_host(["o " + " ".join(str(int(f.get(n, 0))) for n in S.INT_FIELDS) for f in S.entries(part)]):
+            why, lab, choice, launch = line.split("\t")
+            assert why == "" and choice.startswith("family=") and launch.startswith("chunk=")
+            assert by_label.setdefault(lab, choice) == choice and by_choice.setdefault(choice, lab) == lab, (lab, choice, by_label.get(lab), by_choice.get(choice))
+    assert len(by_label) == len(by_choice) >= 40
+
+
 # ---- plan construction and weight packing against the recorded ones (tests/plan_sweep.py) ----------------------------------------
 
 @pytest.fixture(scope="module")

@@ -97,7 +97,8 @@ WG_CASES = [  # name, B,H,W, Cin,CinT,cin_off, Cout,CoutT,cout_off, k, stride, s
     ("linear_100_of_128", 1, 700, 1, 100, 128, 0, 2048, 2048, 0, 1, 1, False),
     ("linear_logits", 1, 300, 1, 256, 256, 0, 1091, 1104, 0, 1, 1, False),
     ("odd_hw", 1, 15, 17, 24, 24, 0, 48, 48, 0, 3, 1, False),
-    # Wo % 32 == 0: with 16-bit copies of both operands these run on the nine-taps-in-one-workgroup kernel (wgrad3_kernel)
+    # Wo % 32 == 0: with 16-bit copies of both operands these run on the nine-taps-in-one-workgroup kernels (wgrad3t_kernel; the slices case, not 8-channel
+    # aligned, on the staged wgrad3_kernel)
     ("c3n_64_256_w64", 2, 6, 64, 64, 64, 0, 256, 256, 0, 3, 1, False),
     ("c3n_288_192_w32", 1, 5, 32, 288, 288, 0, 192, 192, 0, 3, 1, False),
     ("c3n_slices_w96", 1, 4, 96, 40, 72, 32, 100, 128, 8, 3, 1, False),
@@ -106,6 +107,7 @@ WG_CASES = [  # name, B,H,W, Cin,CinT,cin_off, Cout,CoutT,cout_off, k, stride, s
     ("thin_1_of_9", 2, 12, 16, 192, 192, 0, 1, 9, 3, 3, 1, False),
     ("thin_2_of_9", 3, 9, 11, 64, 72, 8, 2, 9, 5, 3, 1, False),
     ("thin_1x1", 2, 40, 40, 96, 96, 0, 2, 2, 0, 1, 1, False),
+    ("thin_1x1_1_of_9", 2, 9, 7, 24, 24, 0, 1, 9, 3, 1, 1, False),
     # SE-gated input with one or two splits per image: the gate multiplies the partial tile's columns instead of the staged elements
     ("se_image_splits", 4, 16, 16, 96, 96, 0, 40, 40, 0, 1, 1, True),
     ("se_image_splits_slices", 3, 16, 8, 72, 80, 8, 136, 136, 0, 1, 1, True),

@@ -50,8 +50,12 @@ def _wg(name, wd, io):
 @pytest.mark.parametrize("wd,io", _WG_CFG, ids=_WG_IDS)
 @pytest.mark.parametrize("case", [c[0] for c in WG_CASES])
 def test_wgrad_exact(case, wd, io):
-    """FTC_OP_WGRAD on WG_CASES x the seven operand-storage configurations of test_wgrad, with the same split choice S: every kernel family behind it
-    (wgrad_kernel, the nine-taps-in-one-workgroup wgrad3_kernel, the thin column-sum kernel, the SE-gated forms) plus the split reduction."""
+    """FTC_OP_WGRAD on WG_CASES x the seven operand-storage configurations of test_wgrad, with the same split choice S.  Which kernels that reaches is
+    proven on the CPU by test_abi_and_plan.test_wgrad_cases_reach_every_kernel_family from the ops' labels (csrc/wgrad_choice.h: the label is the formatted
+    launch): wgrad_kernel on its four tiles and five storage combinations, the nine-tap wgrad3t_kernel (transpose reads) and wgrad3_kernel (staged), the 1x1
+    DMA ring wgrad1t_kernel, wgrad_thin_kernel with 1 and 2 output channels at k = 1 and k = 3, the SE gate applied while staging and to the partial tile --
+    each followed by wgrad_reduce_kernel.  wgrad_reduce_wide_kernel (48 splits and more) is reached by no row: the train-step tests run it.  The tally at the
+    end of the module lists the cases per label."""
     c = _wg(case, wd, io)
     lib = L.load()
     S = int(lib.ftc_wgrad_splits(c.B, c.Ho, c.Wo, c.Cout, c.Cin, c.k))
