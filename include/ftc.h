@@ -103,7 +103,7 @@ typedef enum ftc_op_kind {
        for FTC_OP_BNACT; mean and 1 / sqrt(var + eps) for FTC_OP_BNBWD), and the running statistics aux = fp32 [2][Cin] (mean | var) updated in place:
        r = (1 - momentum) * r + momentum * batch value (the variance unbiased, as torch.nn.BatchNorm2d does).
        w = gamma, bias = beta (fp32 [Cin]); aux0 / aux1 = the bit patterns of the floats eps / momentum; in2 = scratch for the partial sums,
-       float64 [chunks = min(512, ceil(B*H*W / 256))][2][Cin] (2 launches: partial sums, finalize) */
+       float64 [chunks = min(512, ceil(B*H*W / 64))][2][Cin] (2 launches: partial sums, finalize) */
     FTC_OP_BNSTAT = 8,
     /* Training-mode BatchNorm, second half + activation (+ stochastic depth + residual): out[b,y,x,c] = act(in * scale[c] + shift[c]);
        with FTC_FLAG_RESIDUAL: out = out * w2[b] + in2 (w2 = fp32 [B] keep-scales of torchvision's StochasticDepth "row" mode, may be NULL = 1).
@@ -130,7 +130,7 @@ typedef enum ftc_op_kind {
     FTC_OP_SCATTER_ROWS = 13,
     /* Backward of BNSTAT + BNACT: incoming gradient g = in[r][cin_off + c] (row stride Cin_total, 0 = Cin) * bias[b][c] + bias2[b][c]
        (both optional: the SE gate and the squeeze-mean gradient of an MBConv block), * w2[b] (optional StochasticDepth keep-scale);
-       t = z * scale + shift; dt = g * act'(t); out (+= with FTC_FLAG_ACCUM) = scale * (dt - mean(dt) - zhat * mean(dt * zhat));
+       t = z * scale + shift; dt = g * act'(t); out (+= with FTC_FLAG_ACCUM, which therefore needs out) = scale * (dt - mean(dt) - zhat * mean(dt * zhat));
        w (gamma grad) += sum dt * zhat, shift (beta grad) += sum dt.  in2 = z [B*H*W][Cin] (in_dtype: fp32, or stored in the 16-bit
        compute type w_dtype as the reference's autocast stores convolution outputs), scale = the [4][Cin] block of BNSTAT,
        aux = scratch float64 [chunks][2][Cin] + fp32 [2][Cin] (chunks as BNSTAT) */
