@@ -717,7 +717,7 @@ __global__ __launch_bounds__(256) void maploss_bwd_kernel(LossBwdP p) {
             d = (om * om) * (om * om) * pr * pr * (pr + 2.0f * sp * (1.0f - pr));
         }
         gp[0] = a_key * 10.0f * inv_n * d;
-        const float w2 = fmaxf(key - 0.85f, 0.f) / (1.f - 0.85f);
+        const float w2 = fmaxf(key - 0.85f, 0.f) / 0.15f;
         if (key > 0.85f) {
             const float d1 = hp[1] - lp[1 * hw], d2 = hp[2] - lp[2 * hw];
             gp[1] = a_size * w2 / w1c * fminf(fmaxf(d1, -1.0f), 1.0f);
@@ -754,7 +754,7 @@ __global__ __launch_bounds__(256) void idloss_bwd_kernel(IdBwdP p) {
         const float key = p.label[b * 5 * p.hw + q];
         const int id = p.idmap[b * 2 * p.hw + q];
         const bool m3 = key > 0.99f && id > 0;
-        const float coef = m3 ? a_id * (fmaxf(key - 0.99f, 0.f) / (1.f - 0.99f)) / w3c : 0.f;
+        const float coef = m3 ? a_id * (fmaxf(key - 0.99f, 0.f) / 0.01f) / w3c : 0.f;
         for (int hd = 0; hd < 3; ++hd) {
             const int m = p.mod[hd];
             float* go = p.gdec + ((long)hd * p.n + r) * p.pad;

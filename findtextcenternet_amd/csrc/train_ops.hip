@@ -177,7 +177,9 @@ __global__ __launch_bounds__(256) void map_loss_kernel(MapLossP p, double* __res
             const float om = 1.f - key;
             acc[0] += (lg + softplusf_(-lg)) * pr * pr * (om * om * om * om);
         }
-        const float w2 = fmaxf(key - 0.85f, 0.f) / (1.f - 0.85f);
+        // the divisors are the reference's: torch divides the float32 tensor by float32(1 - 0.85) = 0.15f (1.f - 0.85f is 0.14999998f, 3.3 units of 2^-24 off;
+        // 1.f - 0.99f is 15.6 off 0.01f); FTC_OP_LOSS_BWD uses the same two constants
+        const float w2 = fmaxf(key - 0.85f, 0.f) / 0.15f;
         if (key > 0.85f) {
             acc[1] += (huber1(hp[1 * p.hs_c], lp[1 * hw]) + huber1(hp[2 * p.hs_c], lp[2 * hw])) * w2;
             acc[2] += w2;
@@ -246,7 +248,7 @@ __global__ __launch_bounds__(256) void id_loss_kernel(IdLossP p, double* __restr
             right += (am == tgt) ? 1 : 0;
         }
         if (lane == 0) {
-            if (m3) { const float w3 = fmaxf(key - 0.99f, 0.f) / (1.f - 0.99f); a_ce += (double)(ce_sum * w3); a_w += (double)w3; }
+            if (m3) { const float w3 = fmaxf(key - 0.99f, 0.f) / 0.01f; a_ce += (double)(ce_sum * w3); a_w += (double)w3; }
             if (m4) { a_tot += 1.0; a_ok += right == 3 ? 1.0 : 0.0; }
         }
     }

@@ -43,9 +43,10 @@ def simple_decoder(sd: Dict[str, torch.Tensor], x: torch.Tensor) -> List[torch.T
     return out
 
 
-def heatmap_loss(true: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
-    """loss_func.py:74-92."""
-    x = logits.float()
+def heatmap_loss(true: torch.Tensor, logits: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """loss_func.py:74-92 (the reference casts with ``.float()``: dtype's default; float64 for a high-precision evaluation of the same form)."""
+    x = logits.to(dtype)
+    true = true.to(dtype)
     pr = torch.sigmoid(x)
     pos = (true >= 1.0).float()
     neg = (true < 1.0).float()
@@ -54,28 +55,32 @@ def heatmap_loss(true: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
     return (pos_loss + neg_loss).mean()
 
 
-def loss_function(fmask, labelmap, idmap, heatmap, decoder_outputs: Sequence[torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """loss_func.py:94-177."""
+def loss_function(fmask, labelmap, idmap, heatmap, decoder_outputs: Sequence[torch.Tensor], dtype: torch.dtype = None) -> Dict[str, torch.Tensor]:
+    """loss_func.py:94-177.  dtype=None: fp32 throughout, as the reference (what g7 pins).  dtype=torch.float64: the masks and the three weight
+    maps are still computed on the float32 labels exactly as the reference computes them (float32 thresholds, float32(0.15) and float32(0.01) as
+    divisors) -- they are data, nothing differentiates through them -- and every sum, loss form and normaliser is evaluated in float64 on
+    float64 heatmap / decoder tensors."""
+    up = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
     key = labelmap[:, 0]
     m1 = key > 0.85
     kf, idf = key.flatten()[fmask], idmap[:, 0].flatten()[fmask]
     m3 = (kf > 0.99) & (idf > 0)
     m4 = (kf == 1) & (idf > 0)
-    w1 = (torch.clamp(key - 0.85, min=0) / (1 - 0.85))[m1]
+    w1 = up((torch.clamp(key - 0.85, min=0) / (1 - 0.85))[m1])
     w1c = torch.clamp(w1.sum(), min=1.0)
-    w2 = torch.clamp(key - 0.85, min=0) / (1 - 0.85)
-    w3 = (torch.clamp(kf - 0.99, min=0) / (1 - 0.99))[m3]
+    w2 = up(torch.clamp(key - 0.85, min=0) / (1 - 0.85))
+    w3 = up((torch.clamp(kf - 0.99, min=0) / (1 - 0.99))[m3])
     w3c = torch.clamp(w3.sum(), min=1.0)
-    out = {"keymap_loss": heatmap_loss(key, heatmap[:, 0]) * 10.0}
+    out = {"keymap_loss": heatmap_loss(key, heatmap[:, 0], dtype or torch.float32) * 10.0}
     hub = torch.nn.HuberLoss(reduction="none")
-    size = (hub(heatmap[:, 1][m1], labelmap[:, 1][m1]) + hub(heatmap[:, 2][m1], labelmap[:, 2][m1])) * w1
+    size = (hub(heatmap[:, 1][m1], up(labelmap[:, 1][m1])) + hub(heatmap[:, 2][m1], up(labelmap[:, 2][m1]))) * w1
     out["size_loss"] = size.sum() / w1c
-    out["textline_loss"] = F.binary_cross_entropy_with_logits(heatmap[:, 3], labelmap[:, 3])
-    out["separator_loss"] = F.binary_cross_entropy_with_logits(heatmap[:, 4], labelmap[:, 4])
+    out["textline_loss"] = F.binary_cross_entropy_with_logits(heatmap[:, 3], up(labelmap[:, 3]))
+    out["separator_loss"] = F.binary_cross_entropy_with_logits(heatmap[:, 4], up(labelmap[:, 4]))
     for i in range(4):
-        bit = ((idmap[:, 1] & (1 << i)) > 0).float()
+        bit = up(((idmap[:, 1] & (1 << i)) > 0).float())
         out[f"code{1 << i}_loss"] = F.binary_cross_entropy_with_logits(heatmap[:, 5 + i], bit, weight=torch.ones_like(bit) + bit * w2 + w2)
-    id_loss = torch.zeros(())
+    id_loss = torch.zeros((), dtype=dtype or torch.float32)
     right = torch.zeros(int(m4.sum()), dtype=torch.long)
     for m, d in zip(MODULO, decoder_outputs):
         ce = F.cross_entropy(d[m3], (idf % m)[m3], reduction="none")
