@@ -45,6 +45,10 @@ TEXT_EXPORTS = ["ftc_text_abi_version", "ftc_text_create", "ftc_text_destroy", "
 FTC_TEXT_COMPACT_ABI_VERSION = 1
 TEXT_COMPACT_EXPORTS = ["ftc_text_compact_abi_version", "ftc_text_predict_compact", "ftc_text_attention_rows"]
 
+# include/ftc_text_rows.h (the row kernels on their own and the GEMM ops of the recognizer's plans, for kernel-level tests)
+FTC_TEXT_ROWS_ABI_VERSION = 1
+TEXT_ROWS_EXPORTS = ["ftc_text_rows_abi_version", "ftc_text_rownorm_rows", "ftc_text_pad_input", "ftc_text_plan_ops"]
+
 
 # include/ftc_ocr.h (page-level OCR glue): again its own version and list
 FTC_OCR_ABI_VERSION = 1
@@ -236,6 +240,10 @@ def load():
     lib.ftc_text_compact_abi_version.restype = i32
     lib.ftc_text_predict_compact.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32), vp, vp]
     lib.ftc_text_attention_rows.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i32, vp, i64, i32, i32, i32, i32, vp]
+    lib.ftc_text_rows_abi_version.restype = i32
+    lib.ftc_text_rownorm_rows.argtypes = [vp] * 11 + [i32, vp, vp, i64, i32, i32, vp]
+    lib.ftc_text_pad_input.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    lib.ftc_text_plan_ops.argtypes = [vp, i32, i32, C.POINTER(Op), i32]
     lib.ftc_ocr_abi_version.restype = i32
     lib.ftc_ocr_assemble.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp, vp]
     lib.ftc_prep_abi_version.restype = i32
@@ -260,6 +268,8 @@ def load():
         raise FtcLibraryError(f"prep ABI mismatch: library {lib.ftc_prep_abi_version()} vs binding {FTC_PREP_ABI_VERSION}")
     if lib.ftc_ocr_abi_version() != FTC_OCR_ABI_VERSION:
         raise FtcLibraryError(f"OCR ABI mismatch: library {lib.ftc_ocr_abi_version()} vs binding {FTC_OCR_ABI_VERSION}")
+    if lib.ftc_text_rows_abi_version() != FTC_TEXT_ROWS_ABI_VERSION:
+        raise FtcLibraryError(f"text rows ABI mismatch: library {lib.ftc_text_rows_abi_version()} vs binding {FTC_TEXT_ROWS_ABI_VERSION}")
     if lib.ftc_text_compact_abi_version() != FTC_TEXT_COMPACT_ABI_VERSION:
         raise FtcLibraryError(f"compact text ABI mismatch: library {lib.ftc_text_compact_abi_version()} vs binding {FTC_TEXT_COMPACT_ABI_VERSION}")
     if lib.ftc_text_abi_version() != FTC_TEXT_ABI_VERSION:

@@ -38,6 +38,7 @@
 #include "ftc_host.h"
 #include "../../include/ftc_text.h"
 #include "../../include/ftc_text_compact.h"
+#include "../../include/ftc_text_rows.h"
 
 hipError_t ftc_text_attention_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad,
                                      float* out, int64_t ldo, int B, int heads, int Sq, int Sk, hipStream_t stream);
@@ -682,6 +683,41 @@ int ftc_text_row_update(int64_t* tokens, const int64_t* codes, const float* scor
     if (B < 1 || B > 65535 || pass < 0 || pass >= FTC_TEXT_PASSES) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_row_update: bad B or pass");
     return PlanBuilder::hip(ftc_text_row_update_launch(tokens, codes, scores, B, pass, done, active, ids, probs, trace_tokens, trace_codes, trace_probs,
                                                        static_cast<hipStream_t>(stream)), "row update");
+}
+
+int ftc_text_rows_abi_version(void) { return FTC_TEXT_ROWS_ABI_VERSION; }
+
+int ftc_text_rownorm_rows(const float* a, const float* b, const float* pos_in, const float* gamma, const float* beta, const float* pos_out,
+                          const int64_t* tokens, const float* e0, const float* e1, const float* e2, const int32_t* tok_row, int tok_rows, float* out,
+                          float* out_pos, int64_t rows, int S_, int E, void* stream) {
+    if ((!a && !tokens) || (tokens && (!e0 || !e1 || !e2)) || (!out && !out_pos) || (out_pos && !pos_out) || (gamma && !beta))
+        return ftc_set_error(FTC_ERR_INVALID, "ftc_text_rownorm_rows: inconsistent pointer arguments");
+    if (rows < 0 || S_ < 1 || E < 64 || E > 1024 || E % 64) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_rownorm_rows: E must be a multiple of 64 in 64..1024, S >= 1");
+    if (tok_row && (!tokens || tok_rows < 1 || (uintptr_t)tok_row % 4))
+        return ftc_set_error(FTC_ERR_INVALID, "ftc_text_rownorm_rows: tok_row needs tokens and tok_rows >= 1");
+    // the entries of tok_row are device data: the kernel checks each against tok_rows before it forms an address
+    return PlanBuilder::hip(ftc_text_rownorm_rows_launch(a, b, pos_in, gamma, beta, pos_out, tokens, e0, e1, e2, tok_row, tok_rows, out, out_pos, rows, S_, E,
+                                                         static_cast<hipStream_t>(stream)), "row kernel");
+}
+
+int ftc_text_pad_input(const float* in, float* rows128, uint8_t* pad, int B, int L, int D, int S_, void* stream) {
+    if (!in || !rows128 || !pad) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_pad_input: null pointer argument");
+    if (D < 1 || D > KPAD || L < 1 || L > S_ || B < 1) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_pad_input: 1 <= D <= 128, 1 <= L <= S and B >= 1");
+    return PlanBuilder::hip(ftc_text_pad_input_launch(in, rows128, pad, B, L, D, S_, static_cast<hipStream_t>(stream)), "input padding");
+}
+
+int ftc_text_plan_ops(ftc_text* h, int B, int n, ftc_op* out, int cap) {
+    if (n < 0 || (n && n >= B) || cap < 0 || (cap && !out)) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_plan_ops: 0 <= n < B, cap >= 0, out needed when cap > 0");
+    std::shared_ptr<TextPlan> p;
+    const int rc = get_plan(h, B, &p, n);
+    if (rc != FTC_OK) return rc;
+    int count = 0;
+    for (const ftc_op& o : p->convs.ops) {      // pushed in the order the steps are built: encoder, key / value, decoder
+        if (o.kind != FTC_OP_CONV) continue;
+        if (count < cap) out[count] = o;
+        ++count;
+    }
+    return count;
 }
 
 }  // extern "C"

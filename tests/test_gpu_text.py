@@ -9,7 +9,10 @@ another summation order); fp16x3 at most 1e-3 of the tensor's range (the contrac
 reference's own bfloat16-autocast run from its float64 run (stored per row); fp16 the bf16 bound.  Kernels: the error of an fp32 sum of
 n independently rounded terms grows like sqrt(n) x 2^-24 x the terms' size; the bounds written at each test are 8 x that.  The select
 kernel is compared BIT FOR BIT (codes, scores, the three largest entries and their indices) with its host restatement
-``ftc_text_select_host``, which runs the same steps in the same order with the same plain-operation exp / log (csrc/text_math.h)."""
+``ftc_text_select_host``, which runs the same steps in the same order with the same plain-operation exp / log (csrc/text_math.h).
+
+tests/test_gpu_text_exact.py holds the attention, row, padding and swiglu kernels and the recognizer's own GEMM ops to BIT EQUALITY on exact operands
+(tests/text_operands.py); the Gaussian tests here stay for what those cannot see, the rounding behaviour on real-valued data."""
 import ctypes as C
 
 import numpy as np
