@@ -47,6 +47,9 @@ TEXT_COMPACT_EXPORTS = ["ftc_text_compact_abi_version", "ftc_text_predict_compac
 
 # include/ftc_text_rows.h (the row kernels on their own and the GEMM ops of the recognizer's plans, for kernel-level tests)
 FTC_TEXT_ROWS_ABI_VERSION = 1
+FTC_TEXT_BWD_ABI_VERSION = 1
+TEXT_BWD_EXPORTS = ["ftc_text_bwd_abi_version", "ftc_text_attention_bwd_workspace_bytes", "ftc_text_attention_bwd", "ftc_text_rownorm_bwd_workspace_bytes",
+                    "ftc_text_rownorm_bwd", "ftc_text_swiglu_bwd", "ftc_text_loss_workspace_bytes", "ftc_text_loss"]
 TEXT_ROWS_EXPORTS = ["ftc_text_rows_abi_version", "ftc_text_rownorm_rows", "ftc_text_pad_input", "ftc_text_plan_ops"]
 
 
@@ -244,6 +247,17 @@ def load():
     lib.ftc_text_rownorm_rows.argtypes = [vp] * 11 + [i32, vp, vp, i64, i32, i32, vp]
     lib.ftc_text_pad_input.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     lib.ftc_text_plan_ops.argtypes = [vp, i32, i32, C.POINTER(Op), i32]
+    lib.ftc_text_bwd_abi_version.restype = i32
+    lib.ftc_text_attention_bwd_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.ftc_text_attention_bwd_workspace_bytes.restype = i64
+    lib.ftc_text_attention_bwd.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp, vp]
+    lib.ftc_text_rownorm_bwd_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.ftc_text_rownorm_bwd_workspace_bytes.restype = i64
+    lib.ftc_text_rownorm_bwd.argtypes = [vp] * 18 + [i64, i32, i32, vp, vp]
+    lib.ftc_text_swiglu_bwd.argtypes = [vp, vp, vp, i64, i32, vp]
+    lib.ftc_text_loss_workspace_bytes.argtypes = [i64]
+    lib.ftc_text_loss_workspace_bytes.restype = i64
+    lib.ftc_text_loss.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     lib.ftc_ocr_abi_version.restype = i32
     lib.ftc_ocr_assemble.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp, vp]
     lib.ftc_prep_abi_version.restype = i32
@@ -268,6 +282,8 @@ def load():
         raise FtcLibraryError(f"prep ABI mismatch: library {lib.ftc_prep_abi_version()} vs binding {FTC_PREP_ABI_VERSION}")
     if lib.ftc_ocr_abi_version() != FTC_OCR_ABI_VERSION:
         raise FtcLibraryError(f"OCR ABI mismatch: library {lib.ftc_ocr_abi_version()} vs binding {FTC_OCR_ABI_VERSION}")
+    if lib.ftc_text_bwd_abi_version() != FTC_TEXT_BWD_ABI_VERSION:
+        raise FtcLibraryError(f"text backward ABI mismatch: library {lib.ftc_text_bwd_abi_version()} vs binding {FTC_TEXT_BWD_ABI_VERSION}")
     if lib.ftc_text_rows_abi_version() != FTC_TEXT_ROWS_ABI_VERSION:
         raise FtcLibraryError(f"text rows ABI mismatch: library {lib.ftc_text_rows_abi_version()} vs binding {FTC_TEXT_ROWS_ABI_VERSION}")
     if lib.ftc_text_compact_abi_version() != FTC_TEXT_COMPACT_ABI_VERSION:

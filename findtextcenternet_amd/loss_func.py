@@ -18,6 +18,7 @@ import torch
 
 from . import _lib as L
 from .schema import modulo_list
+from .text_grad import loss_function3          # noqa: F401  the recognizer's loss (loss_func.py:179-213), under the reference's name
 
 _KEYS = ["loss", "keymap_loss", "size_loss", "textline_loss", "separator_loss", "id_loss", "code1_loss", "code2_loss", "code4_loss",
          "code8_loss", "correct", "total"]
