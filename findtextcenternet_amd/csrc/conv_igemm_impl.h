@@ -1340,6 +1340,7 @@ __global__ __launch_bounds__(128 * WMQ, (WMQ == 2) ? 2 : (CPR == 4 && !UPIN && !
     // align_corners=True, same expression as upcat_kernel; halo pixels outside the image are the conv's zero padding).
     // The corner offsets and weights of a pass do not depend on the channel block: computed once per tile
     // (halo pixels outside the image get out-of-range offsets -> zeros -> the conv's zero padding).
+    // Pinned by tests/test_gpu_exact_upsample.py (one-hot weights: every halo value bit for bit).
     constexpr int NUP = UPIN ? NLH : 1;
     int up_off[NUP][4];
     float up_ly[NUP], up_lx[NUP];
@@ -1684,6 +1685,7 @@ __global__ __launch_bounds__(384 * WMH, 3) void conv3x3_wl1_kernel(const ConvP p
     };
 
     // ---- UPIN: identical to conv3x3_halo_kernel (one 16-byte chunk of the halo image per thread and pass) ----
+    // Pinned by tests/test_gpu_exact_upsample.py (one-hot weights: every halo value bit for bit, plain and walking).
     constexpr int NUP = UPIN ? NLH : 1;
     int up_off[NUP][4];
     float up_ly[NUP], up_lx[NUP];

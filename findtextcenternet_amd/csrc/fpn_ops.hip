@@ -38,6 +38,7 @@ __global__ __launch_bounds__(256) void upcat_kernel(const T* __restrict__ prev, 
             const int b = (int)(row / (unsigned)Ho);
             const int y = (int)(row - (unsigned)b * Ho);
             // ATen upsample_bilinear2d, align_corners=True: src = dst * (in-1)/(out-1)
+            // (pinned by tests/test_gpu_exact_upsample.py: bit for bit on lattice operands, per element on dense ones)
             const float sy = ry * (float)y, sx = rx * (float)x;
             const int y0 = (int)sy, x0 = (int)sx;
             const int y1 = y0 + (y0 < Hi - 1 ? 1 : 0), x1 = x0 + (x0 < Wi - 1 ? 1 : 0);
