@@ -24,6 +24,8 @@ FLAG_SE_HPART = 0x8000000
 FLAG_KBLOCK32 = 0x10000000
 FLAG_PRESPLIT = 0x20000000
 MBHEAD_SLICE = 128
+# the two test bits of ftc_op.flags on STEM, DWCONV, SE, MBHEAD, FMBCONV and UPCAT (csrc/backbone_choice.h): the general kernel / MBHEAD's phase timeline
+BACKBONE_FORCE_GENERAL, BACKBONE_TIMELINE = 0x100, 0x1000
 
 EXPORTS = ["ftc_abi_version", "ftc_last_error", "ftc_device_info", "ftc_plan_create", "ftc_plan_destroy",
            "ftc_plan_num_ops", "ftc_plan_run", "ftc_plan_run_streams", "ftc_plan_profile", "ftc_op_kernel_label", "ftc_conv_signature", "ftc_tune_ops", "ftc_decode_scratch_bytes", "ftc_decode", "ftc_tile_gather", "ftc_paste_maps",

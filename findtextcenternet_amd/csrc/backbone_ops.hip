@@ -695,122 +695,93 @@ __global__ __launch_bounds__(256, 4) void se_fc2_foldx3_kernel(const float* __re
 
 }  // namespace
 
+// The launchers below resolve the op once (backbone_choice.h) and decide nothing else from the ftc_op.  ftc_plan_create refuses every op a resolver refuses, so the
+// hipErrorInvalidValue returns are unreachable through a plan -- keep it that way.
 hipError_t launch_stem(const OpArgs& a, hipStream_t s) {
+    using namespace backbone;
     const ftc_op& o = *a.op;
-    const bool wide = o.Cout % 16 == 0;
-    const long total = (long)o.B * o.Ho * o.Wo * (o.Cout / (wide ? 16 : 4));
-    const int blocks = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    const size_t lds = (size_t)27 * o.Cout * sizeof(float);
+    StemChoice c;
+    if (stem_resolve(o, &c) != nullptr) return hipErrorInvalidValue;
     const int nchw = (o.flags & FTC_FLAG_IN_NCHW) ? 1 : 0;
     const int act = o.act != FTC_ACT_NONE ? 1 : 0;
-#define STEM_LAUNCH(OT, CT, NQ, FAST)                                                                                                        \
-    hipLaunchKernelGGL((stem_kernel<OT, CT, NQ, FAST>), dim3(blocks), dim3(256), lds, s, (const float*)a.in, (const float*)a.w, a.bias, (OT*)a.out, \
-                       (CT*)a.out2, o.B, o.H, o.W, o.Ho, o.Wo, o.Cout, nchw, act)
-#define STEM_WIDTH(OT, CT, FAST) do { if (wide) STEM_LAUNCH(OT, CT, 4, FAST); else STEM_LAUNCH(OT, CT, 1, FAST); } while (0)
-    // fp32 trunk output with an optional 16-bit copy in the plan's compute type (ftc_op.w_dtype: bf16 unless FTC_F16); a plan without
-    // a 16-bit copy or type is the fp32 parity mode (or the training-mode forward): libm's expf
-    if (o.out_dtype == FTC_F32 && o.w_dtype == FTC_F16) STEM_WIDTH(float, _Float16, true);
-    else if (o.out_dtype == FTC_F32 && a.out2) STEM_WIDTH(float, __bf16, true);
-    else if (o.out_dtype == FTC_F32) STEM_WIDTH(float, __bf16, false);
-    else if (o.out_dtype == FTC_F16) STEM_WIDTH(_Float16, _Float16, true);
-    else STEM_WIDTH(__bf16, __bf16, true);
+#define STEM_LAUNCH(OT, CT, NQ, FAST)                                                                                                                  \
+    hipLaunchKernelGGL((stem_kernel<OT, CT, NQ, FAST>), dim3(c.blocks), dim3(256), (size_t)c.lds_bytes, s, (const float*)a.in, (const float*)a.w, a.bias, \
+                       (OT*)a.out, (CT*)a.out2, o.B, o.H, o.W, o.Ho, o.Wo, o.Cout, nchw, act)
+#define STEM_WIDTH(OT, CT, FAST) do { if (c.nq == 4) STEM_LAUNCH(OT, CT, 4, FAST); else STEM_LAUNCH(OT, CT, 1, FAST); } while (0)
+    // fp32 trunk output with an optional 16-bit copy in the plan's compute type; a plan without a 16-bit copy or type is the fp32 parity mode (or the
+    // training-mode forward): libm's expf
+    switch (c.family) {
+    case STEM_F32_EXPF: STEM_WIDTH(float, __bf16, false); break;
+    case STEM_F32_COPY: if (c.copy_dtype == FTC_F16) STEM_WIDTH(float, _Float16, true); else STEM_WIDTH(float, __bf16, true); break;
+    default: if (c.out_dtype == FTC_F16) STEM_WIDTH(_Float16, _Float16, true); else STEM_WIDTH(__bf16, __bf16, true);
+    }
 #undef STEM_WIDTH
 #undef STEM_LAUNCH
     return hipGetLastError();
 }
 
-// stride 1: the strip kernel (16-bit: fast SiLU only; fp32: with or without activation).  0x100: the general kernel (A/B measurements, tests)
-bool ftc_dwconv_strip(const ftc_op& o) { return o.stride == 1 && !(o.flags & 0x100) && (ftc_is16(o.in_dtype) ? o.act != FTC_ACT_NONE : (o.Cin % 4 == 0)); }
-
 hipError_t launch_dwconv(const OpArgs& a, hipStream_t s) {
+    using namespace backbone;
     const ftc_op& o = *a.op;
-    const int TH = o.stride == 1 ? 8 : 4, TW = 8;
-    const int tilesX = (o.Wo + TW - 1) / TW, tilesY = (o.Ho + TH - 1) / TH;
-    const int P = tilesX * tilesY;
-    if (P != o.aux0) return hipErrorInvalidValue;
-    // Consecutive tiles per workgroup: the grid runs in ceil(workgroups / resident slots) rounds of `tpw` tile
-    // times each; take the tpw that minimises rounds * tpw (ties: the larger, it amortises the tap loads).
-    const bool strip = ftc_dwconv_strip(o);
-    const long slabs = (long)((o.Cin + 63) / 64) * o.B;
-    const long slots = 256L * (strip ? (o.in_dtype == FTC_F32 ? 2 : 4) : o.in_dtype == FTC_F32 ? 3 : 2);     // workgroups resident on 256 CUs (LDS / VGPR-limited)
-    int tpw = 1;
-    long best = -1;
-    for (int cand = 1; cand <= (P < 16 ? P : 16); ++cand) {
-        const long wgs = slabs * ((P + cand - 1) / cand);
-        const long cost = ((wgs + slots - 1) / slots) * cand;
-        if (best < 0 || cost <= best) { best = cost; tpw = cand; }
-    }
-    dim3 grid((o.Cin + 63) / 64, (P + tpw - 1) / tpw, o.B);
+    DwconvChoice c;
+    if (dwconv_resolve(o, &c) != nullptr) return hipErrorInvalidValue;
+    const dim3 grid(c.grid[0], c.grid[1], c.grid[2]);
+    const int act = o.act != FTC_ACT_NONE ? 1 : 0;
+#define DW_STRIP_LAUNCH(T, PRECISE)                                                                                              \
+    hipLaunchKernelGGL((dwconv_strip_kernel<T, PRECISE>), grid, dim3(256), 0, s, (const T*)a.in, (const float*)a.w, a.bias, \
+                       (T*)a.out, a.aux, o.H, o.W, o.Cin, c.tilesX, c.P, c.tpw, act)
 #define DW_LAUNCH(T, ST)                                                                                      \
     hipLaunchKernelGGL((dwconv_kernel<T, ST>), grid, dim3(256), 0, s, (const T*)a.in, (const float*)a.w, a.bias, \
-                       (T*)a.out, a.aux, o.H, o.W, o.Ho, o.Wo, o.Cin, tilesX, P, tpw, o.act != FTC_ACT_NONE ? 1 : 0)
-    const int act = o.act != FTC_ACT_NONE ? 1 : 0;
-    if (strip && o.in_dtype == FTC_F32)
-        hipLaunchKernelGGL((dwconv_strip_kernel<float, true>), grid, dim3(256), 0, s, (const float*)a.in, (const float*)a.w, a.bias,
-                           (float*)a.out, a.aux, o.H, o.W, o.Cin, tilesX, P, tpw, act);
-    else if (o.in_dtype == FTC_F32) { if (o.stride == 1) DW_LAUNCH(float, 1); else DW_LAUNCH(float, 2); }
-    else if (strip && o.in_dtype == FTC_F16)
-        hipLaunchKernelGGL((dwconv_strip_kernel<_Float16, false>), grid, dim3(256), 0, s, (const _Float16*)a.in, (const float*)a.w, a.bias,
-                           (_Float16*)a.out, a.aux, o.H, o.W, o.Cin, tilesX, P, tpw, act);
-    else if (strip)
-        hipLaunchKernelGGL((dwconv_strip_kernel<__bf16, false>), grid, dim3(256), 0, s, (const __bf16*)a.in, (const float*)a.w, a.bias,
-                           (__bf16*)a.out, a.aux, o.H, o.W, o.Cin, tilesX, P, tpw, act);
-    else if (o.in_dtype == FTC_F16) { if (o.stride == 1) DW_LAUNCH(_Float16, 1); else DW_LAUNCH(_Float16, 2); }
-    else { if (o.stride == 1) DW_LAUNCH(__bf16, 1); else DW_LAUNCH(__bf16, 2); }
+                       (T*)a.out, a.aux, o.H, o.W, o.Ho, o.Wo, o.Cin, c.tilesX, c.P, c.tpw, act)
+#define DW_STRIDE(T) do { if (c.stride == 1) DW_LAUNCH(T, 1); else DW_LAUNCH(T, 2); } while (0)
+    if (c.family == DW_STRIP) {
+        if (c.dtype == FTC_F32) DW_STRIP_LAUNCH(float, true); else if (c.dtype == FTC_F16) DW_STRIP_LAUNCH(_Float16, false); else DW_STRIP_LAUNCH(__bf16, false);
+    } else {
+        if (c.dtype == FTC_F32) DW_STRIDE(float); else if (c.dtype == FTC_F16) DW_STRIDE(_Float16); else DW_STRIDE(__bf16);
+    }
+#undef DW_STRIDE
 #undef DW_LAUNCH
+#undef DW_STRIP_LAUNCH
     return hipGetLastError();
 }
 
 hipError_t launch_se(const OpArgs& a, hipStream_t s) {
+    using namespace backbone;
     const ftc_op& o = *a.op;
+    SeChoice c;
+    if (se_resolve(o, &c) != nullptr) return hipErrorInvalidValue;
     const int C = o.Cin, S = o.aux0, P = o.aux1;
     float* hidden = const_cast<float*>(static_cast<const float*>(a.in2));      // [B,S] scratch
     // FTC_FLAG_SE_HPART: `aux` = the per-slice fc1 partial products of FTC_OP_MBHEAD, [B][P slices][S]: no fc1 launch
-    const bool hp = (o.flags & FTC_FLAG_SE_HPART) != 0;
-    const float* hpart = hp ? a.aux : nullptr;
-    if (!hp) {
-        hipLaunchKernelGGL(se_fc1_kernel, dim3((S + 7) / 8, o.B), dim3(512), (size_t)C * sizeof(float), s, (const float*)a.aux,
+    const float* hpart = c.hpart ? a.aux : nullptr;
+    if (!c.hpart) {
+        hipLaunchKernelGGL(se_fc1_kernel, dim3(c.fc1_grid[0], c.fc1_grid[1]), dim3(512), (size_t)c.fc1_lds_bytes, s, (const float*)a.aux,
                            (const float*)a.w, a.bias, hidden, C, S, P, 1.0f / (float)(o.H * o.W));
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (hp && (o.flags & FTC_FLAG_SE_FOLD) && (o.flags & 0x100)) return hipErrorInvalidValue;    // (validated: fold64 / foldx3 or no fold)
-    if ((o.flags & FTC_FLAG_SE_FOLD) && o.w_dtype == FTC_F32) {    // fp16x3 plan: pre-split fp32 chunks in, pre-split per-image copies out
-        const int cb = (C + 63) / 64;
-        int nz = (768 + cb * o.B - 1) / (cb * o.B);
-        const int max_nz = (o.Cout_total + 15) / 16;
-        nz = nz < 1 ? 1 : nz > max_nz ? max_nz : nz;
-        hipLaunchKernelGGL(se_fc2_foldx3_kernel, dim3(cb, o.B, nz), dim3(256), (size_t)(((S + 3) & ~3) + 256 + 64) * sizeof(float), s, hidden,
-                           (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const u32x4*)a.in, (u32x4*)a.out2, o.Cout_total, hpart, a.bias, P);
-    } else if ((o.flags & FTC_FLAG_SE_FOLD) && !(o.flags & 0x100)) {
-        const int cb = (C + 63) / 64;
-        int nz = (768 + cb * o.B - 1) / (cb * o.B);                  // ~3 workgroups per CU
-        const int max_nz = (o.Cout_total + 31) / 32;
-        nz = nz < 1 ? 1 : nz > max_nz ? max_nz : nz;
-        if (o.w_dtype == FTC_F16)
-            hipLaunchKernelGGL(se_fc2_fold64_kernel<_Float16>, dim3(cb, o.B, nz), dim3(256), (size_t)(((S + 3) & ~3) + 256 + 64) * sizeof(float), s, hidden,
-                               (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const _Float16*)a.in, (_Float16*)a.out2, o.Cout_total, hpart, a.bias, P);
-        else
-            hipLaunchKernelGGL(se_fc2_fold64_kernel<__bf16>, dim3(cb, o.B, nz), dim3(256), (size_t)(((S + 3) & ~3) + 256 + 64) * sizeof(float), s, hidden,
-                               (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const __bf16*)a.in, (__bf16*)a.out2, o.Cout_total, hpart, a.bias, P);
-    } else if (o.flags & FTC_FLAG_SE_FOLD) {                         // 0x100: the first version (kept for A/B measurements)
-        const int cb = (C + 255) / 256;
-        int nz = 512 / (cb * o.B);
-        nz = nz < 1 ? 1 : nz > 8 ? 8 : nz;
-        if (o.w_dtype == FTC_F16)
-            hipLaunchKernelGGL((se_fc2_kernel<true, _Float16>), dim3(cb, o.B, nz), dim3(256), (size_t)(S + 256) * sizeof(float), s, hidden,
-                               (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const _Float16*)a.in, (_Float16*)a.out2, o.Cout_total, nullptr, nullptr, 0);
-        else
-            hipLaunchKernelGGL((se_fc2_kernel<true, __bf16>), dim3(cb, o.B, nz), dim3(256), (size_t)(S + 256) * sizeof(float), s, hidden,
-                               (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const __bf16*)a.in, (__bf16*)a.out2, o.Cout_total, nullptr, nullptr, 0);
-    } else if (hp && C % 64 == 0 && S <= 160) {
-        // gates only, from FTC_OP_MBHEAD's partial products (round 4: the project convolution applies them to its weight fragments): the
-        // 64-channel kernel with an EMPTY fold -- every load of its prologue in flight at once (the plain kernel below walks S dependent loads)
-        hipLaunchKernelGGL(se_fc2_fold64_kernel<__bf16>, dim3(C / 64, o.B, 1), dim3(256), (size_t)(((S + 3) & ~3) + 256 + 64) * sizeof(float), s, hidden,
-                           (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const __bf16*)nullptr, (__bf16*)nullptr, 0, hpart, a.bias, P);
-    } else {
-        hipLaunchKernelGGL((se_fc2_kernel<false, __bf16>), dim3((C + 255) / 256, o.B), dim3(256), (size_t)S * sizeof(float), s, hidden,
-                           (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const __bf16*)nullptr, (__bf16*)nullptr, 0, hpart, a.bias, P);
+    const dim3 grid(c.grid[0], c.grid[1], c.grid[2]);
+    const size_t lds = (size_t)c.lds_bytes;
+#define SE_FOLD64(T, IN, OUT2, N)                                                                                                                        \
+    hipLaunchKernelGGL(se_fc2_fold64_kernel<T>, grid, dim3(256), lds, s, hidden, (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const T*)(IN), (T*)(OUT2), \
+                       N, hpart, a.bias, P)
+#define SE_FC2(FOLD, T, IN, OUT2, N, HP, B1, NP)                                                                                                         \
+    hipLaunchKernelGGL((se_fc2_kernel<FOLD, T>), grid, dim3(256), lds, s, hidden, (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const T*)(IN), (T*)(OUT2), \
+                       N, HP, B1, NP)
+    switch (c.family) {
+    case SE_FOLDX3:                  // fp16x3 plan: pre-split fp32 chunks in, pre-split per-image copies out
+        hipLaunchKernelGGL(se_fc2_foldx3_kernel, grid, dim3(256), lds, s, hidden, (const float*)a.w2, a.bias2, (float*)a.out, C, S, (const u32x4*)a.in,
+                           (u32x4*)a.out2, o.Cout_total, hpart, a.bias, P);
+        break;
+    case SE_FOLD64: if (c.dtype == FTC_F16) SE_FOLD64(_Float16, a.in, a.out2, o.Cout_total); else SE_FOLD64(__bf16, a.in, a.out2, o.Cout_total); break;
+    case SE_GATES64: SE_FOLD64(__bf16, nullptr, nullptr, 0); break;              // the 64-channel kernel with an EMPTY fold
+    case SE_FC1_FC2_FOLD:            // BACKBONE_FORCE_GENERAL: the first version (kept for A/B measurements)
+        if (c.dtype == FTC_F16) SE_FC2(true, _Float16, a.in, a.out2, o.Cout_total, nullptr, nullptr, 0);
+        else SE_FC2(true, __bf16, a.in, a.out2, o.Cout_total, nullptr, nullptr, 0);
+        break;
+    default: SE_FC2(false, __bf16, nullptr, nullptr, 0, hpart, a.bias, P);      // SE_FC1_FC2, SE_FC2_HPART
     }
+#undef SE_FC2
+#undef SE_FOLD64
     return hipGetLastError();
 }

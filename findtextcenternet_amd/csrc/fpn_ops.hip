@@ -4,6 +4,7 @@
 // Reference: Leafmap.forward (/root/reference/models/detector.py:192-201; nn.UpsamplingBilinear2d
 // at :170/:177 == F.interpolate(mode='bilinear', align_corners=True)) and
 // CenterNetDetector.forward (/root/reference/models/detector.py:289-296).
+#include "backbone_choice.h"
 #include "ftc_common.h"
 
 namespace {
@@ -238,27 +239,31 @@ hipError_t launch_tapsum(const OpArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Resolves the op once (backbone_choice.h); ftc_plan_create refuses every op upcat_resolve refuses, so the hipErrorInvalidValue returns are unreachable
+// through a plan -- keep it that way.
 hipError_t launch_upcat(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
+    backbone::UpcatChoice c;
+    if (backbone::upcat_resolve(o, &c) != nullptr) return hipErrorInvalidValue;
     const int Cy = o.aux0, Ct = o.aux1;
     const int CyT = o.Cin_total > 0 ? o.Cin_total : Cy;     // channel stride of the upsampled tensor
-    const int V = o.in_dtype == FTC_F32 ? 4 : 8;
-    const long total = (long)o.B * o.Ho * o.Wo * ((Cy + Ct) / V);
-    long nb = (total + 255) / 256;
-    if (nb > 16384) nb = 16384;
-    const int G = o.groups > 1 ? o.groups : 1;
+    const int G = c.G;
     const long prev_gs = G == 1 ? 0 : (o.flags & FTC_FLAG_GROUP_IN_SLICE) ? Cy : (long)o.B * o.H * o.W * CyT;
     const long out_gs = G == 1 ? 0 : (long)o.B * o.Ho * o.Wo * (Cy + Ct);
     const float ry = o.Ho > 1 ? (float)(o.H - 1) / (float)(o.Ho - 1) : 0.f;
     const float rx = o.Wo > 1 ? (float)(o.W - 1) / (float)(o.Wo - 1) : 0.f;
 #define UPCAT_LAUNCH(T, TT)                                                                                       \
-    hipLaunchKernelGGL((upcat_kernel<T, TT>), dim3((unsigned)nb, G), dim3(256), 0, s, (const T*)a.in + o.cin_off, (const TT*)a.in2, \
+    hipLaunchKernelGGL((upcat_kernel<T, TT>), dim3(c.nb, G), dim3(256), 0, s, (const T*)a.in + o.cin_off, (const TT*)a.in2, \
                        a.scale, a.shift, (T*)a.out, o.B, o.H, o.W, o.Ho, o.Wo, Cy, Ct, CyT, ry, rx, prev_gs, out_gs)
-    // res_dtype = dtype of the backbone tap (the trunk stays fp32 in bf16 mode)
-    if (o.in_dtype == FTC_F32) UPCAT_LAUNCH(float, float);
-    else if (o.in_dtype == FTC_F16) { if (o.res_dtype == FTC_F32) UPCAT_LAUNCH(_Float16, float); else UPCAT_LAUNCH(_Float16, _Float16); }
-    else if (o.res_dtype == FTC_F32) UPCAT_LAUNCH(__bf16, float);
-    else UPCAT_LAUNCH(__bf16, __bf16);
+    // TT = the type of the backbone tap (the trunk stays fp32 in bf16 mode)
+    switch (c.T * 4 + c.TT) {
+    case FTC_F32 * 4 + FTC_F32: UPCAT_LAUNCH(float, float); break;
+    case FTC_F16 * 4 + FTC_F32: UPCAT_LAUNCH(_Float16, float); break;
+    case FTC_F16 * 4 + FTC_F16: UPCAT_LAUNCH(_Float16, _Float16); break;
+    case FTC_BF16 * 4 + FTC_F32: UPCAT_LAUNCH(__bf16, float); break;
+    case FTC_BF16 * 4 + FTC_BF16: UPCAT_LAUNCH(__bf16, __bf16); break;
+    default: return hipErrorInvalidValue;
+    }
 #undef UPCAT_LAUNCH
     return hipGetLastError();
 }

@@ -121,15 +121,14 @@ const char* validate_op(const ftc_op& o, const ftc_plan* pl, std::string* why) {
     const int64_t pin = (int64_t)o.B * o.H * o.W, pout = (int64_t)o.B * o.Ho * o.Wo;
     if (o.B <= 0 || o.H <= 0 || o.W <= 0) return "B/H/W must be positive";
     switch (o.kind) {
-    case FTC_OP_STEM:
-        if (!need(o.in, true, "in") || !need(o.out, true, "out", pout * o.Cout * es(o.out_dtype)) || !need(o.w, true, "w", (int64_t)27 * o.Cout * 4) ||
-            !need(o.bias, true, "bias", (int64_t)o.Cout * 4)) return why->c_str();
-        if (o.Cout % 4 || o.Cout > 256) return "stem: Cout must be a multiple of 4 (<= 256)";
-        if ((long)o.B * o.Ho * o.Wo * (o.Cout / 4) >= 0x7fffffffL) return "stem: more than 2^31 output quads";
-        if (!need(o.out2, false, "out2", pout * o.Cout * 2)) return why->c_str();
-        if (o.out2.base != FTC_BASE_NULL && o.out_dtype != FTC_F32) return "stem: out2 (16-bit copy) needs an fp32 primary output";
-        if (o.Ho != (o.H - 1) / 2 + 1 || o.Wo != (o.W - 1) / 2 + 1) return "stem: Ho/Wo inconsistent";
+    // STEM, DWCONV, MBHEAD, FMBCONV, SE, UPCAT: the op's form and its kernel choice (backbone_choice.h) come first, then the extents the choice implies
+    case FTC_OP_STEM: {
+        backbone::StemChoice c;
+        if (const char* refused = backbone::stem_resolve(o, &c)) return refused;
+        if (!need(o.in, true, "in") || !need(o.out, true, "out", pout * o.Cout * es(c.out_dtype)) || !need(o.w, true, "w", (int64_t)27 * o.Cout * 4) ||
+            !need(o.bias, true, "bias", (int64_t)o.Cout * 4) || !need(o.out2, false, "out2", pout * o.Cout * 2)) return why->c_str();
         return nullptr;
+    }
     case FTC_OP_CONV: {
         if (o.Cin <= 0 || o.Cout <= 0 || o.Cin_total <= 0 || o.Cout_total <= 0 || o.Ho <= 0 || o.Wo <= 0 || o.ksize <= 0) return "conv: sizes must be positive";
         const bool upin = (o.flags & FTC_FLAG_UPCAT_IN) != 0, topf = (o.flags & FTC_FLAG_TOP_FUSE) != 0;
@@ -156,84 +155,57 @@ const char* validate_op(const ftc_op& o, const ftc_plan* pl, std::string* why) {
             return "conv: KBLOCK32 describes out2 (the 16-bit copy) and needs a 16-bit w_dtype, Cout % 32 == 0, Cout == Cout_total, cout_off == 0, one group";
         return conv_validate(o);
     }
-    case FTC_OP_DWCONV:
-        if (o.in_dtype != FTC_F32 && !ftc_is16(o.in_dtype)) return "dwconv: unknown dtype";
-        if (o.Cin <= 0 || o.aux0 <= 0 || o.Ho <= 0 || o.Wo <= 0) return "dwconv: sizes must be positive";
-        if (!need(o.in, true, "in", pin * o.Cin * es(o.in_dtype)) || !need(o.out, true, "out", pout * o.Cin * es(o.in_dtype)) ||
+    case FTC_OP_DWCONV: {
+        backbone::DwconvChoice c;
+        if (const char* refused = backbone::dwconv_resolve(o, &c)) return refused;
+        if (!need(o.in, true, "in", pin * o.Cin * es(c.dtype)) || !need(o.out, true, "out", pout * o.Cin * es(c.dtype)) ||
             !need(o.w, true, "w", (int64_t)9 * o.Cin * 4) || !need(o.bias, true, "bias", (int64_t)o.Cin * 4) ||
             !need(o.aux, true, "aux", (int64_t)o.B * o.aux0 * o.Cin * 4)) return why->c_str();
-        // the bf16 / fp16 stride-1 strip kernel builds a 32-bit buffer resource per image
-        if (ftc_is16(o.in_dtype) && (int64_t)o.H * o.W * o.Cin * 2 >= 0x7fffffffLL) return "dwconv: one image exceeds the 2 GiB buffer-resource limit";
-        if (o.Cin % (o.in_dtype == FTC_F32 ? 4 : 8) || o.Cin != o.Cout) return "dwconv: C must be a multiple of one 16-byte access (4 fp32 / 8 bf16) and Cin == Cout";
-        if (o.stride != 1 && o.stride != 2) return "dwconv: stride must be 1 or 2";
-        if (o.Ho != (o.H - 1) / o.stride + 1 || o.Wo != (o.W - 1) / o.stride + 1) return "dwconv: Ho/Wo inconsistent";
-        if (o.in_dtype != o.out_dtype) return "dwconv: in/out dtype must match";
         return nullptr;
+    }
     case FTC_OP_MBHEAD: {
-        if (o.Cin <= 0 || o.Cout <= 0) return "mbhead: sizes must be positive";
-        if ((o.flags & FTC_FLAG_PRESPLIT) && o.in_dtype != FTC_F32) return "mbhead: FTC_FLAG_PRESPLIT applies to the fp32-tensor form";
-        if (!ftc_mbhead_legal(o))
-            return "mbhead: needs 16-bit in/out/w of one type (slice width Cout_total = 0 | 128 | 96 dividing Cout) or fp32 with FTC_FLAG_SPLIT16 (Cout % 64 == 0), stride 1, ksize 3, Ho = H, Wo = W, Cin % 32 == 0 and a map (or, with aux1 = "
-                   "output rows per band, a band + 2 halo rows) of <= 576 pixels and < 601 row-separated slots";
-        const int64_t esz = o.in_dtype == FTC_F32 ? 4 : 2;
-        const int64_t nb = ftc_mbhead_bands(o), ns = o.Cout / ftc_mbhead_slice(o);
+        backbone::MbheadChoice c;
+        if (const char* refused = backbone::mbhead_resolve(o, &c)) return refused;
+        const int64_t esz = c.x3 ? 4 : 2, nb = c.nb, ns = c.ns;
         if (!need(o.in, true, "in", pin * o.Cin * esz) || !need(o.out, true, "out", pin * o.Cout * esz) || !need(o.w2, true, "w2", (int64_t)o.Cout * o.Cin * esz) ||
             !need(o.bias2, true, "bias2", (int64_t)o.Cout * 4) || !need(o.w, true, "w", (int64_t)9 * o.Cout * 4) ||
             !need(o.bias, true, "bias", (int64_t)o.Cout * 4) || !need(o.aux, true, "aux", (int64_t)o.B * nb * o.Cout * 4)) return why->c_str();
-        if ((o.scale.base != FTC_BASE_NULL) != (o.out2.base != FTC_BASE_NULL)) return "mbhead: scale (fc1 weight) and out2 (fc1 partial products) come together";
-        if (o.scale.base != FTC_BASE_NULL) {
-            // the kernel forms the partial products of at most 10 passes x 16 = 160 squeeze units (w1r[NU], mbconv_slice.hip); units beyond that were never written
-            if (o.aux0 <= 0 || o.aux0 > FTC_MBHEAD_MAX_SQUEEZE) return "mbhead: aux0 (squeeze width S) must be in 1..160 when the fc1 partial products are requested";
-            if (!need(o.scale, true, "scale", (int64_t)o.aux0 * o.Cout * 4) || !need(o.out2, true, "out2", (int64_t)o.B * nb * ns * o.aux0 * 4)) return why->c_str();
-        }
-        if (o.flags & 0x1000) { if (!need(o.in2, true, "in2", (int64_t)o.B * nb * ns * 256)) return why->c_str(); }      // phase timeline (tools/mbslice_bench.py)
+        if (c.hpart && (!need(o.scale, true, "scale", (int64_t)o.aux0 * o.Cout * 4) || !need(o.out2, true, "out2", (int64_t)o.B * nb * ns * o.aux0 * 4))) return why->c_str();
+        if ((o.flags & backbone::BACKBONE_TIMELINE) && !need(o.in2, true, "in2", (int64_t)o.B * nb * ns * 256)) return why->c_str();      // phase timeline (tools/mbslice_bench.py)
         return nullptr;
     }
     case FTC_OP_FMBCONV: {
-        if (!ftc_fmbconv_legal(o))
-            return "fmbconv: needs 16-bit in / w of one type (or fp32 in / w with FTC_FLAG_SPLIT16 and aux1 = 256), fp32 out, 3x3 stride 1 (Ho = H, Wo = W), Cin % 32 == 0, aux1 (expanded channels) 256 or 384, Cout % 32 == 0 and "
-                   "<= 128, whole tensors (no channel slices, no groups), act = SiLU, flags = RESIDUAL or none";
-        const int64_t E = o.aux1, esz = o.w_dtype == FTC_F32 ? 4 : 2;      // (fp16x3 form: fp32 tensors, pre-split weights, out2 = the pre-split copy)
+        backbone::FmbconvChoice c;
+        if (const char* refused = backbone::fmbconv_resolve(o, &c)) return refused;
+        const int64_t E = c.E, esz = c.x3 ? 4 : 2;      // (fp16x3 form: fp32 tensors, pre-split weights, out2 = the pre-split copy)
         if (!need(o.in, true, "in", pin * o.Cin * esz) || !need(o.out, true, "out", pin * o.Cout * 4) || !need(o.w2, true, "w2", E * 9 * o.Cin * esz) ||
             !need(o.bias2, true, "bias2", E * 4) || !need(o.w, true, "w", (int64_t)o.Cout * E * esz) || !need(o.bias, true, "bias", (int64_t)o.Cout * 4) ||
             !need(o.in2, (o.flags & FTC_FLAG_RESIDUAL) != 0, "in2", pin * o.Cout * 4) || !need(o.out2, false, "out2", pin * o.Cout * esz)) return why->c_str();
         return nullptr;
     }
-    case FTC_OP_SE:
-        if (o.aux0 <= 0 || o.aux1 <= 0 || o.Cin <= 0) return "se: C, S, P must be positive";
-        if (!need(o.aux, true, "aux", (int64_t)o.B * o.aux1 * ((o.flags & FTC_FLAG_SE_HPART) ? o.aux0 : o.Cin) * 4) || !need(o.out, true, "out", (int64_t)o.B * o.Cin * 4) ||
-            !need(o.in2, true, "in2", (int64_t)o.B * o.aux0 * 4) || !need(o.w, !(o.flags & FTC_FLAG_SE_HPART), "w", (int64_t)o.aux0 * o.Cin * 4) ||
+    case FTC_OP_SE: {
+        backbone::SeChoice c;
+        if (const char* refused = backbone::se_resolve(o, &c)) return refused;
+        if (!need(o.aux, true, "aux", (int64_t)o.B * o.aux1 * (c.hpart ? o.aux0 : o.Cin) * 4) || !need(o.out, true, "out", (int64_t)o.B * o.Cin * 4) ||
+            !need(o.in2, true, "in2", (int64_t)o.B * o.aux0 * 4) || !need(o.w, !c.hpart, "w", (int64_t)o.aux0 * o.Cin * 4) ||
             !need(o.w2, true, "w2", (int64_t)o.aux0 * o.Cin * 4) || !need(o.bias, true, "bias", (int64_t)o.aux0 * 4) ||
             !need(o.bias2, true, "bias2", (int64_t)o.Cin * 4)) return why->c_str();
-        if (o.Cin % 4) return "se: C must be a multiple of 4";
-        if ((size_t)o.Cin * 4 > 64000 || (size_t)o.aux0 * 4 > 64000) return "se: C or S too large for LDS";
         if (o.flags & FTC_FLAG_SE_FOLD) {
-            if (o.Cout_total <= 0) return "se: SE_FOLD needs Cout_total (rows of the folded matrix)";
-            const bool x3 = o.w_dtype == FTC_F32 && (o.flags & FTC_FLAG_SPLIT16);      // fp16x3 plan: pre-split fp32 chunks
-            const int64_t eb = x3 ? 4 : 2;
+            const int64_t eb = c.family == backbone::SE_FOLDX3 ? 4 : 2;
             if (!need(o.in, true, "in", (int64_t)o.Cout_total * o.Cin * eb) || !need(o.out2, true, "out2", (int64_t)o.B * o.Cout_total * o.Cin * eb)) return why->c_str();
-            if (o.Cin % 8 || o.Cout_total <= 0 || !(ftc_is16(o.w_dtype) || x3))
-                return "se: SE_FOLD needs a 16-bit (or, with FTC_FLAG_SPLIT16, pre-split fp32) [Cout_total][C] matrix with C % 8 == 0";
         }
         return nullptr;
-    case FTC_OP_UPCAT:
-        if (o.aux0 < 0 || o.aux1 <= 0 || o.Ho <= 0 || o.Wo <= 0) return "upcat: sizes must be positive";
-        {
-            const int64_t cyt = o.Cin_total > 0 ? o.Cin_total : o.aux0;
-            const int64_t in_ext = ((o.flags & FTC_FLAG_GROUP_IN_SLICE) ? 1 : G) * pin * cyt * es(o.in_dtype);
-            if (!need(o.in, o.aux0 > 0, "in", in_ext) || !need(o.in2, true, "in2", pout * o.aux1 * es(o.res_dtype)) ||
-                !need(o.out, true, "out", G * pout * (o.aux0 + o.aux1) * es(o.in_dtype)) || !need(o.scale, true, "scale", G * o.aux1 * 4) ||
-                !need(o.shift, true, "shift", G * o.aux1 * 4)) return why->c_str();
-        }
-        // 16-byte lanes: 4 fp32 / 8 16-bit channels per access, for the channel counts AND the slice of a wider upsampled tensor
-        if (o.aux0 % (o.in_dtype == FTC_F32 ? 4 : 8) || o.aux1 % (o.in_dtype == FTC_F32 ? 4 : 8) || o.aux1 <= 0) return "upcat: channel counts must be multiples of one 16-byte access (4 fp32 / 8 bf16)";
-        if (o.aux0 > 0 && o.Cin_total > 0 && (o.Cin_total % (o.in_dtype == FTC_F32 ? 4 : 8) || o.cin_off % (o.in_dtype == FTC_F32 ? 4 : 8))) return "upcat: channel slice of the upsampled tensor is not 16-byte aligned";
-        if (o.aux0 > 0 && o.Cin_total > 0 && (o.Cin_total % 4 || o.cin_off % 4 || o.cin_off + o.aux0 > o.Cin_total)) return "upcat: bad channel slice of the upsampled tensor";
-        if (o.in_dtype != o.out_dtype) return "upcat: in/out dtype must match";
-        if ((long)o.B * o.Ho * o.Wo * (o.aux0 + o.aux1) / 4 >= 0x7fffffffL) return "upcat: more than 2^31 output chunks per group";
-        if (o.groups < 0 || o.groups > 64 || o.reserved0 != 0) return "upcat: groups must be in 0..64 and reserved0 zero";
-        if ((o.flags & FTC_FLAG_GROUP_IN_SLICE) && (o.groups <= 1 || o.cin_off + o.groups * o.aux0 > o.Cin_total)) return "upcat: GROUP_IN_SLICE channel slices out of range";
+    }
+    case FTC_OP_UPCAT: {
+        backbone::UpcatChoice c;
+        if (const char* refused = backbone::upcat_resolve(o, &c)) return refused;
+        const int64_t cyt = o.Cin_total > 0 ? o.Cin_total : o.aux0;
+        const int64_t in_ext = ((o.flags & FTC_FLAG_GROUP_IN_SLICE) ? 1 : G) * pin * cyt * es(c.T);
+        if (!need(o.in, o.aux0 > 0, "in", in_ext) || !need(o.in2, true, "in2", pout * o.aux1 * es(c.TT)) ||
+            !need(o.out, true, "out", G * pout * (o.aux0 + o.aux1) * es(c.T)) || !need(o.scale, true, "scale", G * o.aux1 * 4) ||
+            !need(o.shift, true, "shift", G * o.aux1 * 4)) return why->c_str();
         return nullptr;
+    }
     case FTC_OP_TAPSUM:
         if (o.aux0 <= 0 || o.aux1 <= 0) return "tapsum: bad aux0 / aux1";
         if (!need(o.in, true, "in", G * pin * o.aux0 * 4) || !need(o.out, true, "out") || !need(o.w, true, "w", (int64_t)o.aux1 * 16) ||
@@ -552,20 +524,9 @@ int ftc_plan_run_streams(const ftc_plan* plan, void* const bases[FTC_NUM_BASES],
 
 int ftc_op_kernel_label(const ftc_op* op, char* buf, int len) {
     if (!op || !buf || len <= 0) return fail(FTC_ERR_INVALID, "ftc_op_kernel_label: null arguments");
+    if (backbone::format_label(*op, buf, len)) return FTC_OK;      // STEM, DWCONV, SE, MBHEAD, FMBCONV, UPCAT: formatted from the choice (backbone_choice.h)
     switch (op->kind) {
-    case FTC_OP_STEM: std::snprintf(buf, len, "stem_kernel"); break;
     case FTC_OP_CONV: conv_kernel_label(*op, buf, len); break;
-    case FTC_OP_DWCONV:
-        if (ftc_dwconv_strip(*op)) std::snprintf(buf, len, "dwconv_strip_kernel<%s,s1>", ftc_dtname(op->in_dtype));
-        else std::snprintf(buf, len, "dwconv_kernel<%s,s%d>", ftc_dtname(op->in_dtype), op->stride);
-        break;
-    case FTC_OP_SE: std::snprintf(buf, len, (op->flags & FTC_FLAG_SE_HPART) ? "se_gate" : "se_fc1+se_fc2"); break;
-    case FTC_OP_MBHEAD:     // two instantiations, as the profiler sees them: the whole 24x24 map (FAST) / the general kernel (bands of rows)
-        std::snprintf(buf, len, "mbconv_slice<%s,%dch,%s>", op->in_dtype == FTC_F32 ? "f16x3" : ftc_dtname(op->in_dtype), ftc_mbhead_slice(*op),
-                      ftc_mbhead_whole_map(*op) ? "24x24" : "bands");
-        break;
-    case FTC_OP_FMBCONV: ftc_fmbconv_label(*op, buf, len); break;
-    case FTC_OP_UPCAT: std::snprintf(buf, len, "upcat_kernel<%s>", ftc_dtname(op->in_dtype)); break;
     case FTC_OP_NMS: std::snprintf(buf, len, "nms_kernel"); break;
     case FTC_OP_TAPSUM: std::snprintf(buf, len, "tapsum_kernel"); break;
     case FTC_OP_BNSTAT: std::snprintf(buf, len, "bnstat_partial+final<%s>", ftc_dtname(op->in_dtype)); break;

@@ -237,14 +237,9 @@ hipError_t launch_loss_bwd(const OpArgs& a, hipStream_t s);
 hipError_t launch_pack_train(const ftc_pack_entry* entries, int n, long max_elems, hipStream_t s);
 int ftc_wgrad_splits_impl(int B, int Ho, int Wo, int Cout, int Cin, int ksize);
 hipError_t launch_se(const OpArgs& a, hipStream_t s);
-// mbconv_slice.hip: FTC_OP_MBHEAD (expand 1x1 + depthwise 3x3 + squeeze, one image x 64 channels per workgroup)
-bool ftc_mbhead_legal(const ftc_op& o);
-int ftc_mbhead_bands(const ftc_op& o);
-int ftc_mbhead_band_rows(int H, int W);
-int ftc_mbhead_slice(const ftc_op& o);         // expanded channels per workgroup (ftc_op.Cout_total, or the form's default)
+// mbconv_slice.hip: FTC_OP_MBHEAD (expand 1x1 + depthwise 3x3 + squeeze, one image x a slice of the expanded channels per workgroup; backbone_choice.h)
 hipError_t launch_mbhead(const OpArgs& a, hipStream_t s);
 hipError_t launch_fmbconv(const OpArgs& a, hipStream_t s);      // fused_mbconv.hip (FTC_OP_FMBCONV)
-const char* ftc_fmbconv_label(const ftc_op& o, char* buf, int len);
 hipError_t launch_upcat(const OpArgs& a, hipStream_t s);
 hipError_t launch_nms(const OpArgs& a, hipStream_t s);
 hipError_t launch_tapsum(const OpArgs& a, hipStream_t s);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/ftc.h"
+#include "backbone_choice.h"
 #include "conv_choice.h"
 #include "wgrad_choice.h"
 
@@ -19,14 +20,8 @@ struct ftc_plan {
 // Records the thread-local message returned by ftc_last_error() and returns `code`.
 int ftc_set_error(int code, const std::string& msg);
 
-// mbconv_slice.hip: shapes FTC_OP_MBHEAD accepts (the plan builder asks before it emits one)
-bool ftc_mbhead_legal(const ftc_op& o);
-int ftc_mbhead_bands(const ftc_op& o);          // workgroup bands per image (1 = the whole map)
-int ftc_mbhead_band_rows(int H, int W);         // ftc_op.aux1 for an H x W map: 0 = whole map, > 0 = output rows per band, -1 = does not fit
-int ftc_mbhead_slice(const ftc_op& o);          // expanded channels per workgroup (ftc_op.Cout_total, or the form's default)
-
-// fused_mbconv.hip: shapes FTC_OP_FMBCONV accepts (the plan builder asks before it emits one)
-bool ftc_fmbconv_legal(const ftc_op& o);
+// backbone_choice.h: the kernel choice of FTC_OP_STEM, DWCONV, SE, MBHEAD, FMBCONV and UPCAT (backbone::<kind>_resolve + <kind>_format_label) and the geometry
+// the plan builder asks before it emits an op (ftc_mbhead_legal, ftc_mbhead_band_rows, ftc_mbhead_bands, ftc_mbhead_slice, ftc_fmbconv_legal, ...)
 
 // conv_igemm.hip: NULL if the convolution op (incl. its tuned kernel choice ftc_op.aux0) is supported, else the reason
 // (conv_choice.h: the choice itself, and conv_pinned_choice / conv_small_tile_choice, which write one back into aux0)
@@ -40,11 +35,6 @@ void wgrad_kernel_label(const ftc_op& op, char* buf, int len);
 hipError_t ftc_allow_dyn_lds(const void* kernel, int bytes);
 // ftc_api.hip: compute units of the current device (asked once per device)
 hipError_t ftc_device_cus(int* n_cu);
-
-// Kernel picks that ftc_op_kernel_label restates: one predicate each, called by the launcher and by the label
-bool ftc_dwconv_strip(const ftc_op& o);         // backbone_ops.hip: FTC_OP_DWCONV runs the stride-1 strip kernel
-bool ftc_mbhead_whole_map(const ftc_op& o);     // mbconv_slice.hip: FTC_OP_MBHEAD runs the whole-24x24-map instantiation (both forms)
-int ftc_fmbconv_bk(const ftc_op& o);            // fused_mbconv.hip: K step of the 16-bit FTC_OP_FMBCONV kernel
 
 // page_merge.hip: the header block in the scratch of the rank-ordered page selections (ftc_page_merge; ftc_page_fill in page_fill.hip) and the two
 // of its kernels both use -- the exclusive prefix sum of the neighbour counts (more edges than `cap`: use_seq = 1) and the kept ranks -> keep_idx

@@ -510,57 +510,35 @@ static hipError_t launch_fmb_x3(FmbP p, hipStream_t s) {
 
 }  // namespace convimpl
 
-// Shapes FTC_OP_FMBCONV accepts (the plan builder asks before it emits one): 16-bit operands of one type, fp32 output (+ optional 16-bit copy), 3x3
-// stride 1 "same", Cin % 32 == 0, E = aux1 in {256, 384}, Cout % 32 == 0 and <= 128; every byte offset inside one 2 GiB buffer resource.
-bool ftc_fmbconv_legal(const ftc_op& o) {
-    const int E = o.aux1;
-    const long px = (long)o.B * o.H * o.W;
-    if (o.w_dtype == FTC_F32)               // the fp16x3 form: fp32 tensors with FTC_FLAG_SPLIT16, E = 256, out2 = the optional PRE-SPLIT copy
-        return (o.flags & FTC_FLAG_SPLIT16) && o.in_dtype == FTC_F32 && o.out_dtype == FTC_F32 && o.ksize == 3 && o.stride == 1 && o.Ho == o.H && o.Wo == o.W && o.Cin > 0 &&
-               o.Cin % 32 == 0 && E == 256 && o.Cout > 0 && o.Cout % 32 == 0 && o.Cout <= 128 && o.Cin_total == o.Cin && o.cin_off == 0 && o.Cout_total == o.Cout &&
-               o.cout_off == 0 && o.groups <= 1 && o.act == FTC_ACT_SILU && (o.flags & ~(FTC_FLAG_RESIDUAL | FTC_FLAG_SPLIT16)) == 0 &&
-               (!(o.flags & FTC_FLAG_RESIDUAL) || o.res_dtype == FTC_F32) && px * o.Cin * 4 < 0x7fffffffL && px > 0 && px < 0x7fffffffL / 128;
-    return ftc_is16(o.w_dtype) && o.in_dtype == o.w_dtype && o.out_dtype == FTC_F32 && o.ksize == 3 && o.stride == 1 && o.Ho == o.H && o.Wo == o.W &&
-           o.Cin > 0 && o.Cin % 32 == 0 && (E == 256 || E == 384) && o.Cout > 0 && o.Cout % 32 == 0 && o.Cout <= 128 && o.Cin_total == o.Cin && o.cin_off == 0 &&
-           o.Cout_total == o.Cout && o.cout_off == 0 && o.groups <= 1 && o.act == FTC_ACT_SILU && (o.flags & ~(FTC_FLAG_RESIDUAL)) == 0 &&
-           (!(o.flags & FTC_FLAG_RESIDUAL) || o.res_dtype == FTC_F32) && px * o.Cin * 2 < 0x7fffffffL && px > 0 && px < 0x7fffffffL / 128;
-}
-
-int ftc_fmbconv_bk(const ftc_op& o) { return o.Cin % 64 == 0 ? 64 : 32; }
-
-const char* ftc_fmbconv_label(const ftc_op& o, char* buf, int len) {
-    if (o.w_dtype == FTC_F32) std::snprintf(buf, len, "fmbconv_fused<f16x3,e=%d,bk=32>", o.aux1);
-    else std::snprintf(buf, len, "fmbconv_fused<%s,e=%d,bk=%d>", o.w_dtype == FTC_F16 ? "f16" : "bf16", o.aux1, ftc_fmbconv_bk(o));
-    return buf;
-}
-
+// Resolves the op once (backbone_choice.h: the shapes FTC_OP_FMBCONV accepts, its K step and its label) and decides nothing else from the ftc_op.
+// ftc_plan_create refuses every op fmbconv_resolve refuses, so the hipErrorInvalidValue returns are unreachable through a plan -- keep it that way.
 hipError_t launch_fmbconv(const OpArgs& a, hipStream_t s) {
     using namespace convimpl;
     const ftc_op& o = *a.op;
-    if (!ftc_fmbconv_legal(o)) return hipErrorInvalidValue;
+    backbone::FmbconvChoice c;
+    if (backbone::fmbconv_resolve(o, &c) != nullptr) return hipErrorInvalidValue;
     FmbP p;
     p.x = a.in; p.w1 = a.w2; p.b1 = a.bias2; p.w2 = a.w; p.b2 = a.bias;
     p.res = (o.flags & FTC_FLAG_RESIDUAL) ? static_cast<const float*>(a.in2) : nullptr;
     p.out = static_cast<float*>(a.out); p.out2 = a.out2;
-    p.B = o.B; p.H = o.H; p.W = o.W; p.Cin = o.Cin; p.E = o.aux1; p.Cout = o.Cout;
+    p.B = o.B; p.H = o.H; p.W = o.W; p.Cin = o.Cin; p.E = c.E; p.Cout = o.Cout;
     p.M = o.B * o.H * o.W;
-    const long es = o.w_dtype == FTC_F32 ? 4 : 2;
+    const long es = c.x3 ? 4 : 2;
     p.x_bytes = (unsigned)((long)p.M * o.Cin * es);
     p.w1_bytes = (unsigned)((long)p.E * 9 * o.Cin * es);
     p.w2_bytes = (unsigned)((long)o.Cout * p.E * es);
-    if (o.w_dtype == FTC_F32) {
-        p.ncb = o.Cin / 32;
-        p.nk = 9 * p.ncb;
-        return launch_fmb_x3(p, s);
-    }
-    const int bk = ftc_fmbconv_bk(o);
-    p.ncb = o.Cin / bk;
-    p.nk = 9 * p.ncb;
+    p.ncb = c.ncb;
+    p.nk = c.nk;
+    if (c.x3) return launch_fmb_x3(p, s);
     p.nblk = 0;
-    const bool h = o.w_dtype == FTC_F16;
+    const bool h = c.dtype == FTC_F16;
 #define FMB_GO(BK_, SN_) return h ? launch_fmb<_Float16, BK_, SN_, 2, 1>(p, s) : launch_fmb<__bf16, BK_, SN_, 2, 1>(p, s)
-    if (p.E == 256) { if (bk == 64) FMB_GO(64, 2); FMB_GO(32, 2); }
-    if (bk == 64) FMB_GO(64, 3);
-    FMB_GO(32, 3);
+    switch (c.sn * 100 + c.bk) {
+    case 264: FMB_GO(64, 2);
+    case 232: FMB_GO(32, 2);
+    case 364: FMB_GO(64, 3);
+    case 332: FMB_GO(32, 3);
+    default: return hipErrorInvalidValue;
+    }
 #undef FMB_GO
 }

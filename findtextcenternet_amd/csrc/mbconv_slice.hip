@@ -53,25 +53,19 @@ struct MbsP {
 };
 
 constexpr int MS_NT = 512;                  // threads
-constexpr int MS_MAXPX = 576;               // pixels per image (36 MFMA pixel blocks of 16)
-constexpr int MS_XS = MS_MAXPX * 64;        // bytes of the x part of a stage (64-byte rows: K step 32)
-constexpr int MS_NSTAGE = 3;
-constexpr int MS_MAXSLOT = 601;             // pixel slots of the expanded image (24 x 25 + 1)
+// (backbone_choice.h: MS_MAXPX = 576 pixels and MS_MAXSLOT = 601 pixel slots per workgroup, MS_XS, MS_NSTAGE and the LDS sizes MsLds<NCT>, which the
+// op's resolver shares with this kernel)
+using backbone::MS_MAXPX, backbone::MS_MAXSLOT, backbone::MS_XS, backbone::MS_NSTAGE;
 constexpr int MS_R = 6;                     // outputs per depthwise strip (12: 3.5 instead of 4 reads per output, but 44 registers spilled)
 // Slice width (round 5): NCT channel tiles of 16 per wave = 32 NCT expanded channels per workgroup.  128 (NCT = 4) is the default; 96 (NCT = 3) for
 // blocks whose 128-channel slices leave CUs without a workgroup: stage 6 at batch 8 is 8 x 24 = 192 workgroups on 256 CUs, 8 x 32 = 256 with 96.
-template <int NCT> struct MsGeom {
-    static constexpr int CC = NCT * 32;                  // expanded channels per workgroup
-    static constexpr int CQN = CC / 4;                   // channel quads = lanes per depthwise strip lane group (32 | 24)
+template <int NCT> struct MsGeom : backbone::MsLds<NCT> {       // (CC, STAGE, PITCH, IMG, RING, CONST, LDS: backbone_choice.h)
+    using L = backbone::MsLds<NCT>;
+    static constexpr int CQN = L::CC / 4;                // channel quads = lanes per depthwise strip lane group (32 | 24)
     static constexpr int NPL = MS_NT / CQN;              // depthwise strip lanes (16 | 21; threads beyond NPL * CQN idle through that phase)
-    static constexpr int STAGE = MS_XS + CC * 64;
-    static constexpr int PITCH = CC * 2 + 8;             // bytes per slot
-    static constexpr int IMG = MS_MAXSLOT * PITCH, RING = MS_NSTAGE * STAGE;
-    static constexpr int CONST = ((IMG > RING ? IMG : RING) + 15) / 16 * 16;      // depthwise weights [9][CC] + bias [CC] fp32, behind image and ring
-    static constexpr int LDS = CONST + 10 * CC * 4;
-    static constexpr int NPIECE = 36 + CC / 16;          // DMA pieces of a stage: 36 of x, CC / 16 of weights (44 | 42)
+    static constexpr int NPIECE = 36 + L::CC / 16;       // DMA pieces of a stage: 36 of x, CC / 16 of weights (44 | 42)
     static constexpr int NW6 = NPIECE - 40;              // waves that issue six pieces (the others five)
-    static_assert(LDS <= 160 * 1024 && NPIECE > 40 && NPIECE <= 48, "");
+    static_assert(L::LDS <= 160 * 1024 && NPIECE > 40 && NPIECE <= 48, "");
 };
 
 __device__ __forceinline__ f32x4 mfma16x16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
@@ -88,7 +82,7 @@ template <int N> struct MsInt { static constexpr int value = N; };
 // the whole 24x24 map of the 768x768 plans, H and W compile-time) and MS_BAND48 (the bands of a 48-wide map, the other shape of those
 // plans: W compile-time).  With a compile-time width the row offsets of the depthwise window are instruction immediates and the
 // divisions are by constants.
-constexpr int MS_GENERAL = 0, MS_MAP24 = 1, MS_BAND48 = 2;
+using backbone::MS_GENERAL, backbone::MS_MAP24, backbone::MS_BAND48;      // (enum MbheadFamily, backbone_choice.h)
 
 // (Two forms of the SqueezeExcitation INSIDE this launch were built, measured and removed: round 4's FTC_FLAG_SE_INLINE -- gated output, plain
 // project GEMM: 60.0 vs 41.7 + 14.9 us -- and round 5's FTC_FLAG_SE_TAIL -- ungated output, the last workgroups of an image fold the project
@@ -421,65 +415,33 @@ __global__ __launch_bounds__(MS_NT, 2) void mbconv_slice_kernel(const MbsP p) {
 
 }  // namespace
 
-// rows of the expanded image a workgroup holds: the whole map, or a band of aux1 output rows plus a halo row above and below
-static int mbhead_rows(const ftc_op& o) { return o.aux1 > 0 ? (o.aux1 + 2 < o.H ? o.aux1 + 2 : o.H) : o.H; }
+hipError_t launch_mbhead_x3(const OpArgs& a, const backbone::MbheadChoice& c, hipStream_t s);
 
-bool ftc_mbhead_legal(const ftc_op& o) {
-    const int rows = mbhead_rows(o);
-    const bool x3 = o.in_dtype == FTC_F32 && (o.flags & FTC_FLAG_SPLIT16);          // the fp32-tensor form (csrc/mbconv_slice_x3.hip): 64-channel slices
-    const int slice = ftc_mbhead_slice(o);
-    if (x3 ? slice != FTC_MBHEAD_SLICE_F32 : (slice != 128 && slice != 96)) return false;
-    return (ftc_is16(o.in_dtype) || x3) && o.in_dtype == o.out_dtype && o.in_dtype == o.w_dtype && o.stride == 1 && o.ksize == 3 && o.Ho == o.H &&
-           o.Wo == o.W && o.aux1 >= 0 && rows * o.W <= MS_MAXPX && rows * (o.W + 1) + 1 <= MS_MAXSLOT && o.Cout > 0 &&
-           o.Cout % slice == 0 && o.Cin > 0 && o.Cin % 32 == 0;
-}
-
-// expanded channels per workgroup: ftc_op.Cout_total when given (128 | 96; 64 in the fp32-tensor form), else the default of the form
-int ftc_mbhead_slice(const ftc_op& o) { return o.Cout_total > 0 ? o.Cout_total : (o.in_dtype == FTC_F32 ? FTC_MBHEAD_SLICE_F32 : FTC_MBHEAD_SLICE); }
-
-int ftc_mbhead_bands(const ftc_op& o) { return o.aux1 > 0 ? (o.H + o.aux1 - 1) / o.aux1 : 1; }
-
-// Band height for a map that does not fit a workgroup whole: as many output rows as leave room for the two halo rows (0 = the map fits)
-int ftc_mbhead_band_rows(int H, int W) {
-    if (H * W <= MS_MAXPX && H * (W + 1) + 1 <= MS_MAXSLOT) return 0;
-    int r = MS_MAXPX / W;
-    while (r > 2 && r * (W + 1) + 1 > MS_MAXSLOT) --r;
-    return r - 2 > 0 ? r - 2 : -1;
-}
-
-// the FAST instantiation holds the whole 24x24 map in one workgroup (one band).  0x100: the general kernel (tests)
-bool ftc_mbhead_whole_map(const ftc_op& o) { return o.H == 24 && o.W == 24 && ftc_mbhead_bands(o) == 1 && !(o.flags & 0x100); }
-
-// the band form of the 48-wide maps (stages 4-5 of the 768x768 plans).  0x100: the general kernel (tests)
-static bool ftc_mbhead_band48(const ftc_op& o) { return o.aux1 > 0 && o.W == 48 && !(o.flags & 0x100); }
-
-hipError_t launch_mbhead_x3(const OpArgs& a, hipStream_t s);
-
+// Resolves the op once (backbone_choice.h) and decides nothing else from the ftc_op.  ftc_plan_create refuses every op mbhead_resolve refuses, so the
+// hipErrorInvalidValue return is unreachable through a plan -- keep it that way.
 hipError_t launch_mbhead(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
-    if (!ftc_mbhead_legal(o)) return hipErrorInvalidValue;
-    if (o.in_dtype == FTC_F32) return launch_mbhead_x3(a, s);
+    backbone::MbheadChoice c;
+    if (backbone::mbhead_resolve(o, &c) != nullptr) return hipErrorInvalidValue;
+    if (c.x3) return launch_mbhead_x3(a, c, s);
     MbsP p;
     p.x = a.in; p.we = a.w2; p.be = a.bias2; p.wd = static_cast<const float*>(a.w); p.bd = a.bias; p.out = a.out; p.sums = a.aux;
     p.w1 = a.scale; p.hpart = a.scale ? static_cast<float*>(a.out2) : nullptr;
     p.B = o.B; p.H = o.H; p.W = o.W; p.K = o.Cin; p.C = o.Cout; p.S = o.aux0;
     p.kblock = (o.flags & FTC_FLAG_KBLOCK32) ? 1 : 0;
-    p.R = o.aux1 > 0 ? o.aux1 : o.H; p.nb = ftc_mbhead_bands(o);
+    p.R = c.R; p.nb = c.nb;
     p.img_bytes = (unsigned)((long)o.H * o.W * o.Cin * 2);
     p.inv_hw = 1.0f / (float)(o.H * o.W);
-    p.tl = (o.flags & 0x1000) ? reinterpret_cast<unsigned long long*>(const_cast<void*>(a.in2)) : nullptr;      // phase timeline (tools/mbslice_bench.py)
-    const int slice = ftc_mbhead_slice(o);
-    const int nblk = o.B * p.nb * (o.Cout / slice);
-    const int form = ftc_mbhead_whole_map(o) ? MS_MAP24 : ftc_mbhead_band48(o) ? MS_BAND48 : MS_GENERAL;
+    p.tl = (o.flags & backbone::BACKBONE_TIMELINE) ? reinterpret_cast<unsigned long long*>(const_cast<void*>(a.in2)) : nullptr;      // phase timeline (tools/mbslice_bench.py)
     hipError_t e = hipSuccess;
-#define MBS_LAUNCH(T, F, N) do {                                                                                                   \
-        if ((e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(mbconv_slice_kernel<T, F, N>), MsGeom<N>::LDS)) == hipSuccess) \
-            hipLaunchKernelGGL((mbconv_slice_kernel<T, F, N>), dim3(nblk), dim3(MS_NT), MsGeom<N>::LDS, s, p);                  \
+#define MBS_LAUNCH(T, F, N) do {                                                                                              \
+        if ((e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(mbconv_slice_kernel<T, F, N>), c.lds_bytes)) == hipSuccess) \
+            hipLaunchKernelGGL((mbconv_slice_kernel<T, F, N>), dim3(c.nblk), dim3(MS_NT), c.lds_bytes, s, p);                \
     } while (0)
-#define MBS_PICK(T, N) do { if (form == MS_MAP24) MBS_LAUNCH(T, MS_MAP24, N); else if (form == MS_BAND48) MBS_LAUNCH(T, MS_BAND48, N); \
+#define MBS_PICK(T, N) do { if (c.family == MS_MAP24) MBS_LAUNCH(T, MS_MAP24, N); else if (c.family == MS_BAND48) MBS_LAUNCH(T, MS_BAND48, N); \
                             else MBS_LAUNCH(T, MS_GENERAL, N); } while (0)
-    if (o.in_dtype == FTC_F16) { if (slice == 96) MBS_PICK(_Float16, 3); else MBS_PICK(_Float16, 4); }
-    else { if (slice == 96) MBS_PICK(__bf16, 3); else MBS_PICK(__bf16, 4); }
+    if (c.dtype == FTC_F16) { if (c.slice == 96) MBS_PICK(_Float16, 3); else MBS_PICK(_Float16, 4); }
+    else { if (c.slice == 96) MBS_PICK(__bf16, 3); else MBS_PICK(__bf16, 4); }
 #undef MBS_PICK
 #undef MBS_LAUNCH
     return e != hipSuccess ? e : hipGetLastError();

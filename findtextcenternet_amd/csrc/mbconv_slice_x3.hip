@@ -41,17 +41,14 @@ struct MbxP {
     float inv_hw;
 };
 
-constexpr int X3_CC = FTC_MBHEAD_SLICE_F32;  // expanded channels per workgroup (64)
+using backbone::X3_CC;                       // expanded channels per workgroup (64)
 constexpr int X3_NT = 512;
 constexpr int X3_HALF = 288;                 // pixels per sub-step (18 MFMA blocks of 16)
 constexpr int X3_XS = X3_HALF * 128;         // bytes of an x ring slot (128-byte rows: K step 32)
 constexpr int X3_WS = X3_CC * 128;           // bytes of a weight ring slot
 constexpr int X3_NSTAGE = 3;
 constexpr int X3_WRING = X3_NSTAGE * X3_XS;  // the weight ring sits behind the x ring
-constexpr int X3_MAXSLOT = 601;
-constexpr int X3_PITCH = X3_CC * 4 + 8;      // 264
-constexpr int X3_CONST = (X3_MAXSLOT * X3_PITCH + 15) / 16 * 16;
-constexpr int X3_LDS = X3_CONST + 10 * X3_CC * 4;
+using backbone::X3_MAXSLOT, backbone::X3_PITCH, backbone::X3_CONST, backbone::X3_LDS;      // 601 slots of 264 bytes, the constants behind them (backbone_choice.h)
 static_assert(X3_WRING + X3_NSTAGE * X3_WS <= X3_MAXSLOT * X3_PITCH && X3_LDS <= 160 * 1024, "");
 constexpr int X3_R = 6;
 
@@ -337,19 +334,19 @@ __global__ __launch_bounds__(X3_NT, 2) void mbconv_slice_x3_kernel(const MbxP p)
 
 }  // namespace
 
-hipError_t launch_mbhead_x3(const OpArgs& a, hipStream_t s) {
+// (launch_mbhead, mbconv_slice.hip, resolved the op: the choice is all that is decided here)
+hipError_t launch_mbhead_x3(const OpArgs& a, const backbone::MbheadChoice& c, hipStream_t s) {
     const ftc_op& o = *a.op;
     MbxP p;
     p.x = a.in; p.we = a.w2; p.be = a.bias2; p.wd = static_cast<const float*>(a.w); p.bd = a.bias; p.out = static_cast<float*>(a.out); p.sums = a.aux;
     p.w1 = a.scale; p.hpart = a.scale ? static_cast<float*>(a.out2) : nullptr;
     p.B = o.B; p.H = o.H; p.W = o.W; p.K = o.Cin; p.C = o.Cout; p.S = o.aux0;
-    p.R = o.aux1 > 0 ? o.aux1 : o.H; p.nb = ftc_mbhead_bands(o);
+    p.R = c.R; p.nb = c.nb;
     p.presplit_out = (o.flags & FTC_FLAG_PRESPLIT) ? 1 : 0;
     p.img_bytes = (unsigned)((long)o.H * o.W * o.Cin * 4);
     p.inv_hw = 1.0f / (float)(o.H * o.W);
-    const int nblk = o.B * p.nb * (o.Cout / X3_CC);
-    auto kern = ftc_mbhead_whole_map(o) ? mbconv_slice_x3_kernel<true> : mbconv_slice_x3_kernel<false>;
-    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(kern), X3_LDS); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(X3_NT), X3_LDS, s, p);
+    auto kern = c.family == backbone::MS_MAP24 ? mbconv_slice_x3_kernel<true> : mbconv_slice_x3_kernel<false>;
+    if (hipError_t e = ftc_allow_dyn_lds(reinterpret_cast<const void*>(kern), c.lds_bytes); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(c.nblk), dim3(X3_NT), c.lds_bytes, s, p);
     return hipGetLastError();
 }

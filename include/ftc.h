@@ -81,19 +81,26 @@ typedef struct ftc_ref {
 
 typedef enum ftc_op_kind {
     /* conv3x3 stride 2 on the 3-channel image with x*2-1 fused (CenterNetDetection.forward,
-       detector.py:218) + folded BN + SiLU  -- features[0] */
+       detector.py:218) + folded BN + SiLU  -- features[0].
+       ftc_plan_create refuses an op whose in_dtype, out_dtype, w_dtype or res_dtype is none of FTC_F32, FTC_BF16, FTC_F16 (so it does for
+       DWCONV, SE, UPCAT, MBHEAD and FMBCONV: csrc/backbone_choice.h holds what each of the six accepts and the kernel it runs) */
     FTC_OP_STEM = 1,
     /* dense 1x1 / 3x3 convolution as im2col-free implicit GEMM on MFMA, NHWC, with fused
        per-channel bias (folded BN), activation, residual add, optional per-(image,channel)
        SE scale on the input, channel-sliced input and output (free concat) */
     FTC_OP_CONV = 2,
     /* depthwise 3x3 (stride 1|2) + folded BN + SiLU, plus per-(image,channel) partial sums of
-       the output for the SE squeeze */
+       the output for the SE squeeze.  aux0 must be the tile count ceil(Wo / 8) * ceil(Ho / (stride == 1 ? 8 : 4)) -- the kernels lay the
+       partial sums out by it -- and every dtype field one of FTC_F32, FTC_BF16, FTC_F16: ftc_plan_create refuses anything else */
     FTC_OP_DWCONV = 3,
-    /* SE excitation: mean of the partial sums -> fc1+bias -> SiLU -> fc2+bias -> sigmoid */
+    /* SE excitation: mean of the partial sums -> fc1+bias -> SiLU -> fc2+bias -> sigmoid.
+       ftc_plan_create refuses FTC_FLAG_SE_HPART | FTC_FLAG_SE_FOLD together with the test bit 0x100 (the first fold kernel, which that bit selects, has
+       no partial-product loader) and a dtype field that is none of FTC_F32, FTC_BF16, FTC_F16 */
     FTC_OP_SE = 4,
     /* FPN level input: bilinear x2 (align_corners=True) of the previous level, concatenated with
-       the per-head BatchNorm of the backbone tap (Leafmap.forward, detector.py:192-201) */
+       the per-head BatchNorm of the backbone tap (Leafmap.forward, detector.py:192-201).
+       in_dtype == out_dtype; res_dtype (the tap) is FTC_F32 or in_dtype: ftc_plan_create refuses any other pair (an fp32 op with a 16-bit tap, a
+       16-bit op with a tap of the other 16-bit type) and a dtype field that is none of FTC_F32, FTC_BF16, FTC_F16 */
     FTC_OP_UPCAT = 5,
     /* 3x3 max-pool NMS on heatmap channel 0 -> channel 1 (CenterNetDetector.forward,
        detector.py:291-296) */
@@ -179,13 +186,15 @@ typedef enum ftc_op_kind {
        aux = [B][nb][Cout] per-band channel sums (FTC_OP_SE: aux1 = nb) and out2 = [B][nb * Cout/FTC_MBHEAD_SLICE][aux0].
        Round 5 (ABI 9): Cout_total = the slice width (0 = the default: 128; 96 where 128-channel slices leave CUs idle), Cout % slice == 0, out2 and
        FTC_OP_SE's aux1 count Cout / slice slices; the fp32-tensor form (in_dtype = out_dtype = w_dtype = FTC_F32 with FTC_FLAG_SPLIT16, csrc/mbconv_slice_x3.hip):
-       `in` and w2 PRE-SPLIT (see FTC_FLAG_PRESPLIT), 64-channel slices, fp32 `out` (pre-split with FTC_FLAG_PRESPLIT) */
+       `in` and w2 PRE-SPLIT (see FTC_FLAG_PRESPLIT), 64-channel slices, fp32 `out` (pre-split with FTC_FLAG_PRESPLIT).
+       Every dtype field, res_dtype included, is one of FTC_F32, FTC_BF16, FTC_F16: ftc_plan_create refuses anything else */
     FTC_OP_MBHEAD = 25,
     /* Fused-MBConv block with expansion (torchvision FusedMBConv, expand_ratio != 1; /root/reference/models/detector.py:14-16) in one launch
        (csrc/fused_mbconv.hip):  e = act(conv3x3(in) + bias2)  [Cin -> E = aux1, 3x3 stride 1 "same"],  out = conv1x1(e) + bias (+ in2)  [E -> Cout].
        in [B,H,W,Cin] 16-bit, w2 [E][9][Cin] (K-major, same type), bias2 fp32 [E], w [Cout][E] (same type), bias fp32 [Cout], in2 fp32 [B,H,W,Cout]
        with FTC_FLAG_RESIDUAL, out fp32 [B,H,W,Cout], out2 = optional 16-bit copy of out (NHWC).  e is rounded to the 16-bit type exactly as
-       the two-launch form stores it, but never leaves the CU.  Cin % 32 == 0, aux1 in {256, 384}, Cout % 32 == 0, Cout <= 128, act = FTC_ACT_SILU. */
+       the two-launch form stores it, but never leaves the CU.  Cin % 32 == 0, aux1 in {256, 384}, Cout % 32 == 0, Cout <= 128, act = FTC_ACT_SILU.
+       Every dtype field, res_dtype included, is one of FTC_F32, FTC_BF16, FTC_F16: ftc_plan_create refuses anything else */
     FTC_OP_FMBCONV = 26,
     FTC_OP_TAPSUM = 7          /* second half of a 3x3 convolution split as per-pixel taps + 9-point sum (FTC_FLAG_TOP_FUSE):
                                   out[b,y,x,ch_j] = bias[j] + sum_{r,s} in[g_j][b,y+r-1,x+s-1][(3r+s)*co_j + o_j] (zero outside),

@@ -589,6 +589,130 @@ def test_wgrad_labels_and_choices_correspond_one_to_one(wgrad_choice_host):
     assert len(by_label) == len(by_choice) >= 40
 
 
+# ---- the kernel choice of FTC_OP_STEM, DWCONV, SE, MBHEAD, FMBCONV and UPCAT (csrc/backbone_choice.h) -------------------------------------------
+
+@pytest.mark.parametrize("part", ["plans", "cases", "grid", "refused"])
+def test_backbone_choice_sweep_matches_the_recorded_one(part):
+    """Which ops ftc_plan_create accepts, the full error text of the others and every kernel label, entry by entry against part "choices" of
+    tests/golden/backbone_choices.json.gz."""
+    import backbone_choice_sweep as S
+    gold = S.load_golden()
+    want = gold["choices"][part]
+    ents = S.entries(part)
+    got = S.replay(part)
+    assert len(got) == len(want) == len(ents) > 0
+    for i, ((lab, err), (li, ei)) in enumerate(zip(got, want)):
+        assert err == (None if ei < 0 else gold["errors"][ei]), (part, i, ents[i])
+        assert err is not None or lab == gold["labels"][li], (part, i, ents[i])          # (a refused op has no choice to label)
+    if part == "refused":
+        assert not any(err is None for _, err in got)
+        prefixes = {S.KIND_NAME[f["kind"]] + ": " for f in ents}
+        assert all(any(p in err for p in prefixes) for _, err in got)                    # every reason keeps its kind prefix
+
+
+def test_backbone_choices_equal_the_ones_before_the_resolvers():
+    """Parts plans, cases and grid against "stage1", recorded from the commit before csrc/backbone_choice.h: the same ops accepted under the same labels,
+    the same ops refused -- except the ops the rules of NEWLY_REFUSED name, which are refused now, each with (one of) the reason(s) its rule(s) give."""
+    import backbone_choice_sweep as S
+    gold = S.load_golden()
+    hit = {name: 0 for name, _, _ in S.NEWLY_REFUSED}
+    for part in ("plans", "cases", "grid"):
+        ents = S.entries(part)
+        assert len(ents) == len(gold["stage1"][part]) == len(gold["choices"][part])
+        for i, (f, (li1, ok1), (li, ei)) in enumerate(zip(ents, gold["stage1"][part], gold["choices"][part])):
+            if ok1 and ei >= 0:
+                reasons = S.newly_refused(f)
+                assert any(gold["errors"][ei].endswith(r) for r in reasons), (part, i, f, gold["errors"][ei], reasons)
+                for name, rule, _ in S.NEWLY_REFUSED:
+                    hit[name] += bool(rule(f))
+            else:
+                assert bool(ok1) == (ei < 0) and (not ok1 or gold["labels"][li1] == gold["labels"][li]), (part, i, f)
+                assert not (ok1 and S.newly_refused(f)), (part, i, f)
+    assert all(hit.values()), hit                                # every rule refuses something the library used to accept
+    assert all(ei < 0 for _, ei in gold["choices"]["plans"])     # no op of a plan of ours is among them
+
+
+@pytest.fixture(scope="module")
+def backbone_choice_host(tmp_path_factory):
+    """tests/c_abi/backbone_choice_host.cc (plain C++ over csrc/backbone_choice.h alone, its own main) built with AddressSanitizer + UBSan; returns a function
+    that runs it on sweep entries and returns its output lines split at the tabs: [reason, label, instantiation, launch]."""
+    import subprocess
+    import backbone_choice_sweep as S
+    exe = str(tmp_path_factory.mktemp("backbone_choice") / "backbone_choice_host")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "c_abi", "backbone_choice_host.cc"), "-o", exe], check=True)
+
+    def run(ents):
+        r = subprocess.run([exe], input="".join(S.host_line(f) + "\n" for f in ents), capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [line.split("\t") for line in r.stdout.split("\n")[:-1]]
+        assert len(lines) == len(ents) and all(len(line) == 4 for line in lines)
+        return lines
+    return run
+
+
+def test_backbone_choice_header_is_host_only_and_clean_under_sanitizers(backbone_choice_host):
+    """csrc/backbone_choice.h needs no HIP header: the stand-alone program resolves and labels every op of the recorded sweeps, refuses what the library
+    refused for the reason the library gave, and labels the others as the library did."""
+    import backbone_choice_sweep as S
+    gold = S.load_golden()
+    for part in S.PARTS:
+        ents = S.entries(part)
+        want = gold["choices"][part]
+        for f, (why, lab, _, _), (li, ei) in zip(ents, backbone_choice_host(ents), want):
+            assert (why == "" and lab == gold["labels"][li]) if ei < 0 else (why != "" and gold["errors"][ei].endswith(why)), (part, f, why, lab)
+
+
+def test_backbone_gpu_cases_reach_the_forms_their_names_say(backbone_choice_host):
+    """The kernel form behind each named case of the GPU suites, which no label shows: the SE forms of test_gpu_se_bits.FORMS (and fc2_plain_hpart) and of
+    test_se_saturated, and the band48 / band / fast / whole groups of test_gpu_mbhead_bits.py."""
+    import backbone_choice_sweep as S
+    import test_gpu_exact_mbconv as EM
+    import test_gpu_mbhead_bits as MB
+    import test_gpu_se_bits as SB
+    want = {"fold64_bf16": "family=fold64 T=bf16 fc1=0", "fold64_f16": "family=fold64 T=f16 fc1=0", "foldx3": "family=foldx3 T=- fc1=0", "gates64": "family=gates64 T=- fc1=0",
+            "fc2_plain": "family=fc1+fc2 T=- fc1=1", "fold_v1_bf16": "family=fc1+fc2_fold T=bf16 fc1=1", "fc2_plain_hpart": "family=fc2_hpart T=- fc1=0"}
+    assert {n for n, *_ in SB.FORMS} | {"fc2_plain_hpart"} == set(want) == {c["form"] for c in SB.CASES}
+    for c, (why, _, inst, _) in zip(SB.CASES, backbone_choice_host([S.se_bits_fields(c) for c in SB.CASES])):
+        assert why == "" and inst == want[c["form"]], (c["id"], why, inst)
+    sat = {("gates", False): ["family=fc1+fc2 T=- fc1=1"], ("gates", True): ["family=gates64 T=- fc1=0", "family=fc2_hpart T=- fc1=0"],
+           ("fold_v1_bf16", False): ["family=fc1+fc2_fold T=bf16 fc1=1"], ("fold_v1_f16", False): ["family=fc1+fc2_fold T=f16 fc1=1"]}
+    sat.update({(f"fold_{t}", hp): [f"family=fold64 T={t} fc1={int(not hp)}"] for t in ("bf16", "f16") for hp in (False, True)})
+    sat.update({("fold_f16x3", hp): [f"family=foldx3 T=- fc1={int(not hp)}"] for hp in (False, True)})
+    seen = set()
+    for p in S.params(EM.test_se_saturated):
+        named = S.se_sat_fields(p["case"], p["hpart"])
+        for (name, _), (why, _, inst, _) in zip(named, backbone_choice_host([f for _, f in named])):
+            assert why == "" and inst in sat[(name, p["hpart"])], (p, name, why, inst)
+            seen.add(inst)
+    assert seen == {i for v in sat.values() for i in v}          # (both kernels behind "gates" on partial products included)
+    group = {"band48": "family=band48", "band": "family=general", "fast": "family=map24", "whole": "family=general"}
+    for c, (why, _, inst, launch) in zip(MB.CASES, backbone_choice_host([S.mbhead_bits_fields(c) for c in MB.CASES])):
+        assert why == "" and inst == f"{group[c['path']]} slice={c['slice']} T={'bf16' if c['dt'] == L.BF16 else 'f16'}", (c["id"], why, inst)
+        assert f" nb={c['nb']} " in launch and f"hpart={int(c['hp'])} " in launch, (c["id"], launch)
+        assert (c["nb"] > 1) == (c["path"] in ("band48", "band")), c["id"]
+
+
+def test_backbone_gpu_cases_reach_every_kernel_instantiation(backbone_choice_host):
+    """Every family of every kind, with every template argument it has, is what at least one case of the GPU suites (part "cases") runs."""
+    import backbone_choice_sweep as S
+    cases = S.case_entries()
+    got = {}
+    for (test, cid, f), (why, _, inst, _) in zip(cases, backbone_choice_host([f for _, _, f in cases])):
+        if why == "":
+            got.setdefault((S.KIND_NAME[f["kind"]], inst), f"{test} {cid}")
+    want = [("stem", f"family={fam} out={o} copy={c} nq={nq} fast={int(fam > 0)}") for fam, o, c in ((0, "f32", "bf16"), (1, "f32", "bf16"), (1, "f32", "f16"), (2, "bf16", "bf16"), (2, "f16", "f16"))
+            for nq in (1, 4)]
+    want += [("dwconv", f"family=strip T={t} stride=1") for t in ("f32", "bf16", "f16")] + [("dwconv", f"family=general T={t} stride={s}") for t in ("f32", "bf16", "f16") for s in (1, 2)]
+    want += [("se", "family=fc1+fc2 T=- fc1=1"), ("se", "family=fc2_hpart T=- fc1=0"), ("se", "family=gates64 T=- fc1=0"), ("se", "family=foldx3 T=- fc1=0"), ("se", "family=foldx3 T=- fc1=1")]
+    want += [("se", f"family=fold64 T={t} fc1={fc1}") for t in ("bf16", "f16") for fc1 in (0, 1)] + [("se", f"family=fc1+fc2_fold T={t} fc1=1") for t in ("bf16", "f16")]
+    want += [("mbhead", f"family={fam} slice={sl} T={t}") for fam in ("map24", "band48", "general") for sl in (128, 96) for t in ("bf16", "f16")]
+    want += [("mbhead", f"family={fam} slice=64 T=f16x3") for fam in ("map24", "general")]
+    want += [("fmbconv", f"T={t} E={E} bk={bk} sn={2 if E == 256 else 3}") for t in ("bf16", "f16") for E in (256, 384) for bk in (32, 64)] + [("fmbconv", "T=f16x3 E=256 bk=32 sn=0")]
+    want += [("upcat", f"T={t} TT={tt} V={4 if t == 'f32' else 8}") for t, tt in (("f32", "f32"), ("bf16", "f32"), ("bf16", "bf16"), ("f16", "f32"), ("f16", "f16"))]
+    assert sorted(got) == sorted(want), (sorted(set(want) - set(got)), sorted(set(got) - set(want)))
+
+
 # ---- plan construction and weight packing against the recorded ones (tests/plan_sweep.py) ----------------------------------------
 
 @pytest.fixture(scope="module")

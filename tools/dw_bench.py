@@ -4,7 +4,7 @@
     python tools/dw_bench.py [--batch 8] [--reps 20]
 
 Each shape runs as a single-op plan through the C ABI (HIP-event time from ftc_plan_profile); `old` = the
-8-channel-per-lane kernel (op flag 0x100), `new` = the default selection."""
+8-channel-per-lane kernel (op flag BACKBONE_FORCE_GENERAL), `new` = the default selection."""
 import argparse
 import ctypes as C
 import os
@@ -44,7 +44,7 @@ def main():
         ws[off[2]:off[2] + Cc * 4].view(torch.float32).normal_(0, 0.1)
         row = f"{name:22s} {2 * n * 2 / 1e6:7.1f} MB "
         outs = []
-        for label, flags in (("old", 0x100), ("new", 0)):
+        for label, flags in (("old", L.BACKBONE_FORCE_GENERAL), ("new", 0)):
             op = (L.Op * 1)()
             o = op[0]
             o.kind, o.flags, o.act = L.OP_DWCONV, flags, L.ACT_SILU
