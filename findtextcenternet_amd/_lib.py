@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libftc_hip.so")
 
-FTC_ABI_VERSION = 12
+FTC_ABI_VERSION = 13
 F32, BF16, F16 = 0, 1, 2
 (BASE_NULL, BASE_WORKSPACE, BASE_WEIGHTS, BASE_INPUT, BASE_HEATMAP, BASE_FEATURES, BASE_GRADS, NUM_BASES) = range(8)
 OP_STEM, OP_CONV, OP_DWCONV, OP_SE, OP_UPCAT, OP_NMS, OP_TAPSUM, OP_BNSTAT, OP_BNACT = 1, 2, 3, 4, 5, 6, 7, 8, 9
@@ -24,6 +24,8 @@ FLAG_SE_HPART = 0x8000000
 FLAG_KBLOCK32 = 0x10000000
 FLAG_PRESPLIT = 0x20000000
 MBHEAD_SLICE = 128
+NUM_OPERANDS = 11
+OPERAND_UNUSED, OPERAND_OPTIONAL, OPERAND_REQUIRED = 0, 1, 2
 # the two test bits of ftc_op.flags on STEM, DWCONV, SE, MBHEAD, FMBCONV and UPCAT (csrc/backbone_choice.h): the general kernel / MBHEAD's phase timeline
 BACKBONE_FORCE_GENERAL, BACKBONE_TIMELINE = 0x100, 0x1000
 
@@ -34,7 +36,7 @@ EXPORTS = ["ftc_abi_version", "ftc_last_error", "ftc_device_info", "ftc_plan_cre
            "ftc_model_plan", "ftc_model_op_info", "ftc_plan_op",
            "ftc_topk_mask", "ftc_mask_compact", "ftc_gather_rows", "ftc_decoder_workspace_bytes", "ftc_decoder_forward",
            "ftc_glyph_select", "ftc_glyph_decode_workspace_bytes", "ftc_glyph_decode",
-           "ftc_losses_scratch_bytes", "ftc_losses", "ftc_cov_weighting_step", "ftc_pack_train_weights", "ftc_wgrad_splits"]
+           "ftc_losses_scratch_bytes", "ftc_losses", "ftc_cov_weighting_step", "ftc_pack_train_weights", "ftc_wgrad_splits", "ftc_op_extents"]
 
 # include/ftc_text.h (the text recognizer): its own version and its own list; FTC_ABI_VERSION and EXPORTS above describe include/ftc.h only
 FTC_TEXT_ABI_VERSION = 1
@@ -95,6 +97,9 @@ class Op(C.Structure):
         "kind", "flags", "act", "in_dtype", "out_dtype", "w_dtype", "B", "H", "W", "Ho", "Wo", "Cin", "Cin_total",
         "cin_off", "Cout", "Cout_total", "cout_off", "ksize", "stride", "aux0", "aux1", "res_dtype", "groups", "reserved0")] + [
         (n, Ref) for n in ("in_", "in2", "out", "w", "w2", "bias", "bias2", "scale", "shift", "aux", "out2")]
+
+
+REFS = tuple(n for n, t in Op._fields_ if t is Ref)          # the eleven operands, in the order of ftc_op (and of ftc_op_extents)
 
 
 class Tensor(C.Structure):
@@ -222,6 +227,7 @@ def load():
     lib.ftc_cov_weighting_step.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.ftc_pack_train_weights.argtypes = [vp, i32, i64, vp]
     lib.ftc_wgrad_splits.argtypes = [i32] * 6
+    lib.ftc_op_extents.argtypes = [C.POINTER(Op), C.POINTER(i64), C.POINTER(C.c_int32)]
     lib.ftc_text_abi_version.restype = i32
     lib.ftc_text_create.argtypes = [C.POINTER(Tensor), i32, C.POINTER(TextDims), i32, C.POINTER(vp)]
     lib.ftc_text_destroy.argtypes = [vp]
@@ -296,6 +302,13 @@ def load():
         raise FtcLibraryError(f"ABI mismatch: library {lib.ftc_abi_version()} vs binding {FTC_ABI_VERSION}")
     _lib = lib
     return lib
+
+
+def op_extents(op: Op):
+    """ftc_op_extents: (bytes, state) of the eleven operands of `op`, in the order of REFS; FtcError for an op whose form is refused."""
+    nbytes, state = (C.c_int64 * NUM_OPERANDS)(), (C.c_int32 * NUM_OPERANDS)()
+    check(load().ftc_op_extents(C.byref(op), nbytes, state), "ftc_op_extents")
+    return list(nbytes), list(state)
 
 
 def check(rc: int, what: str = "") -> None:

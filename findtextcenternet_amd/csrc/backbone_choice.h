@@ -2,7 +2,7 @@
 // choice struct or the reason the op is refused.  validate_op (plan creation), ftc_op_kernel_label (what tests, tools and bench.py read) and the launcher
 // (what runs) all consume that one result; tests/golden/backbone_choices.json.gz pins it, tests/c_abi/backbone_choice_host.cc prints it.
 // Host only: ftc.h and the standard library, no HIP header and no kernel -- a plain C++ program can include it.  A resolver checks an op's FORM (its int
-// fields, its flags and which optional operands are given); the extents of its buffers are validate_op's, computed from the choice.
+// fields, its flags and which optional operands are given); the extents of its buffers are op_extents.h's, computed from the choice.
 //
 // The forms.  A label names less than a choice: labels are what bench.py and the committed profiles key on and stay as they are.
 //   FTC_OP_STEM     stem_kernel<OutT, CopyT, NQ, FAST>: out fp32 | bf16 | fp16; CopyT = the type of the optional 16-bit copy out2 (fp16 when w_dtype is, else

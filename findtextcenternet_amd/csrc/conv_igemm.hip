@@ -27,39 +27,6 @@ void conv_kernel_label(const ftc_op& op, char* buf, int len) {
     conv_format_label(op, c, buf, len);
 }
 
-const char* conv_validate(const ftc_op& op) {
-    if (op.ksize != 1 && op.ksize != 3) return "conv: ksize must be 1 or 3";
-    if (op.stride != 1 && op.stride != 2) return "conv: stride must be 1 or 2";
-    for (int dt : {op.w_dtype, op.in_dtype, op.out_dtype})
-        if (dt != FTC_F32 && dt != FTC_BF16 && dt != FTC_F16) return "conv: unknown dtype";
-    if (ftc_is16(op.w_dtype) && ((ftc_is16(op.in_dtype) && op.in_dtype != op.w_dtype) || (ftc_is16(op.out_dtype) && op.out_dtype != op.w_dtype)))
-        return "conv: 16-bit input / output must be in the compute type (bf16 and fp16 do not mix)";
-    if ((op.flags & FTC_FLAG_RESIDUAL) && ftc_is16(op.res_dtype) && op.res_dtype != (op.w_dtype == FTC_F16 ? FTC_F16 : FTC_BF16))
-        return "conv: a 16-bit residual must be in the compute type";
-    const int E = op.w_dtype == FTC_F32 ? 4 : 8;
-    const int Ein = op.in_dtype == FTC_F32 ? 4 : 8;
-    if (op.w_dtype == FTC_F32 && (op.in_dtype != FTC_F32)) return "conv: fp32 compute needs fp32 input";
-    if (op.w_dtype == FTC_F32 && (op.out_dtype != FTC_F32)) return "conv: fp32 compute needs fp32 output";
-    if (op.Cin % E) return "conv: Cin must be a multiple of the 16-byte chunk";
-    if (op.Cin_total % Ein || op.cin_off % E) return "conv: input channel stride/offset not 16-byte aligned";
-    if (!(op.flags & FTC_FLAG_UPCAT_IN) && op.cin_off + op.Cin > op.Cin_total) return "conv: input channel slice out of range";
-    if (op.cout_off + op.Cout > op.Cout_total) return "conv: output channel slice out of range";
-    const int pad = (op.ksize - 1) / 2;
-    if (op.Ho != (op.H + 2 * pad - op.ksize) / op.stride + 1 || op.Wo != (op.W + 2 * pad - op.ksize) / op.stride + 1)
-        return "conv: Ho/Wo inconsistent with H/W/ksize/stride";
-    if ((op.flags & FTC_FLAG_SE_SCALE) && op.ksize != 1) return "conv: SE scale only on 1x1";
-    if ((op.flags & FTC_FLAG_SPLIT16) && op.w_dtype != FTC_F32) return "conv: SPLIT16 (fp16x3) applies to fp32 operands";
-    if ((op.flags & FTC_FLAG_BORDER_BIAS) && (op.ksize != 3 || op.stride != 1)) return "conv: border-bias table only for 3x3 stride 1";
-    if ((long)op.B * op.Ho * op.Wo > 0x7fffffffL / 4) return "conv: too many output pixels";
-    // buffer addressing is 32-bit: keep every operand below 2 GiB
-    const long in_bytes = (long)op.B * op.H * op.W * op.Cin_total * (op.in_dtype == FTC_F32 ? 4 : 2);
-    const long w_bytes = (long)op.Cout * op.ksize * op.ksize * op.Cin * (op.w_dtype == FTC_F32 ? 4 : 2);
-    if (in_bytes >= 0x7ff00000L || w_bytes >= 0x7ff00000L) return "conv: operand larger than 2 GiB (split the batch)";
-    if ((op.flags & FTC_FLAG_W_PER_IMAGE) && (op.flags & (FTC_FLAG_SE_SCALE | FTC_FLAG_BORDER_BIAS))) return "conv: per-image weight sets exclude SE_SCALE / BORDER_BIAS";
-    ConvChoice c;
-    return conv_resolve(op, &c);
-}
-
 hipError_t launch_conv(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
     ConvChoice c;

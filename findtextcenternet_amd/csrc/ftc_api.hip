@@ -110,234 +110,19 @@ bool ref_ok(const ftc_ref& r, const ftc_plan* pl, bool required, int64_t extent,
     return true;
 }
 
+// The op's form and the state and extent of each operand come from op_extents (op_extents.h); here every used operand is held to its base.
 const char* validate_op(const ftc_op& o, const ftc_plan* pl, std::string* why) {
-    auto need = [&](const ftc_ref& r, bool req, const char* name, int64_t extent = 0) -> bool {
+    OpExtents e;
+    if (const char* refused = op_extents(o, &e)) return refused;
+    for (int i = 0; i < FTC_NUM_OPERANDS; ++i) {
         std::string w;
-        if (!ref_ok(r, pl, req, extent, &w)) { *why = std::string(name) + ": " + w; return false; }
-        return true;
-    };
-    auto es = [](int dt) -> int64_t { return dt == FTC_F32 ? 4 : 2; };
-    const int64_t G = o.groups > 1 ? o.groups : 1;
-    const int64_t pin = (int64_t)o.B * o.H * o.W, pout = (int64_t)o.B * o.Ho * o.Wo;
-    if (o.B <= 0 || o.H <= 0 || o.W <= 0) return "B/H/W must be positive";
-    switch (o.kind) {
-    // STEM, DWCONV, MBHEAD, FMBCONV, SE, UPCAT: the op's form and its kernel choice (backbone_choice.h) come first, then the extents the choice implies
-    case FTC_OP_STEM: {
-        backbone::StemChoice c;
-        if (const char* refused = backbone::stem_resolve(o, &c)) return refused;
-        if (!need(o.in, true, "in") || !need(o.out, true, "out", pout * o.Cout * es(c.out_dtype)) || !need(o.w, true, "w", (int64_t)27 * o.Cout * 4) ||
-            !need(o.bias, true, "bias", (int64_t)o.Cout * 4) || !need(o.out2, false, "out2", pout * o.Cout * 2)) return why->c_str();
-        return nullptr;
+        if (e.state[i] == FTC_OPERAND_UNUSED || ref_ok(op_operand(o, i), pl, e.state[i] == FTC_OPERAND_REQUIRED, e.bytes[i], &w)) continue;
+        // (the one operand that is refused under the op's name, as it always was)
+        if (o.kind == FTC_OP_LOSS_BWD && i == OPD_OUT2) return "loss_bwd: out2 / aux1 (padded logit row >= 1097, % 4 == 0)";
+        *why = std::string(kOperandName[i]) + ": " + w;
+        return why->c_str();
     }
-    case FTC_OP_CONV: {
-        if (o.Cin <= 0 || o.Cout <= 0 || o.Cin_total <= 0 || o.Cout_total <= 0 || o.Ho <= 0 || o.Wo <= 0 || o.ksize <= 0) return "conv: sizes must be positive";
-        const bool upin = (o.flags & FTC_FLAG_UPCAT_IN) != 0, topf = (o.flags & FTC_FLAG_TOP_FUSE) != 0;
-        const int64_t kk = (int64_t)o.ksize * o.ksize;
-        const int64_t in_ext = upin ? G * o.B * (o.H / 2) * (o.W / 2) * o.Cin_total * es(o.in_dtype) : G * pin * o.Cin_total * es(o.in_dtype);
-        const int64_t in2_ext = upin ? ((o.flags & FTC_FLAG_GROUP_IN2_SHARED) ? 1 : G) * pin * (o.Cin - o.Cin_total) * es(o.in_dtype)
-                                     : pout * o.Cout * es(o.res_dtype);
-        const int64_t w_ext = G * ((o.flags & FTC_FLAG_W_PER_IMAGE) ? o.B : 1) * o.Cout * kk * o.Cin * es(o.w_dtype);
-        const int64_t out_ext = topf ? G * pout * o.aux1 * 4 : ((o.flags & FTC_FLAG_GROUP_OUT_SLICE) ? 1 : G) * pout * o.Cout_total * es(o.out_dtype);
-        if (!need(o.in, true, "in", in_ext) || !need(o.out, true, "out", out_ext) || !need(o.w, true, "w", w_ext) ||
-            !need(o.bias, true, "bias", G * ((o.flags & FTC_FLAG_BORDER_BIAS) ? 16 : 1) * o.Cout * 4)) return why->c_str();
-        if (!need(o.in2, (o.flags & (FTC_FLAG_RESIDUAL | FTC_FLAG_UPCAT_IN)) != 0, "in2", in2_ext) ||
-            !need(o.scale, (o.flags & FTC_FLAG_SE_SCALE) != 0, "scale", (int64_t)o.B * o.Cin * 4)) return why->c_str();
-        const bool x3conv = o.w_dtype == FTC_F32 && (o.flags & FTC_FLAG_SPLIT16);      // out2 = the pre-split copy (4 bytes per element)
-        if (!need(o.out2, false, "out2", pout * o.Cout * (x3conv ? 4 : 2))) return why->c_str();
-        if (!need(o.w2, topf, "w2", G * 32 * o.Cout * (o.w_dtype == FTC_F32 ? 4 : 2))) return why->c_str();
-        if (o.out2.base != FTC_BASE_NULL && (o.out_dtype != FTC_F32 || o.Cout % 4)) return "conv: out2 (bf16 copy) needs an fp32 primary output and Cout % 4 == 0";
-        if ((o.flags & FTC_FLAG_PRESPLIT) && (!x3conv || o.ksize != 1 || (o.flags & (FTC_FLAG_SE_SCALE | FTC_FLAG_UPCAT_IN)) || (o.Cin | o.Cin_total | o.cin_off) % 4))
-            return "conv: FTC_FLAG_PRESPLIT (pre-split input) needs an fp16x3 1x1 convolution without SE scale, channel counts and offsets in whole chunks of 4";
-        if (o.out2.base != FTC_BASE_NULL && o.w_dtype == FTC_F32 && (!x3conv || o.Cout != o.Cout_total || o.cout_off != 0 || G > 1))
-            return "conv: an fp32 convolution writes out2 only as the pre-split copy of an fp16x3 plan (FTC_FLAG_SPLIT16; whole rows, one group)";
-        // out2_index (conv_igemm_impl.h) lays the planes out from Cout alone: no channel slice, no groups, a 16-bit compute type
-        if ((o.flags & FTC_FLAG_KBLOCK32) && (o.out2.base == FTC_BASE_NULL || !ftc_is16(o.w_dtype) || o.Cout % 32 || o.Cout != o.Cout_total || o.cout_off != 0 || G > 1))
-            return "conv: KBLOCK32 describes out2 (the 16-bit copy) and needs a 16-bit w_dtype, Cout % 32 == 0, Cout == Cout_total, cout_off == 0, one group";
-        return conv_validate(o);
-    }
-    case FTC_OP_DWCONV: {
-        backbone::DwconvChoice c;
-        if (const char* refused = backbone::dwconv_resolve(o, &c)) return refused;
-        if (!need(o.in, true, "in", pin * o.Cin * es(c.dtype)) || !need(o.out, true, "out", pout * o.Cin * es(c.dtype)) ||
-            !need(o.w, true, "w", (int64_t)9 * o.Cin * 4) || !need(o.bias, true, "bias", (int64_t)o.Cin * 4) ||
-            !need(o.aux, true, "aux", (int64_t)o.B * o.aux0 * o.Cin * 4)) return why->c_str();
-        return nullptr;
-    }
-    case FTC_OP_MBHEAD: {
-        backbone::MbheadChoice c;
-        if (const char* refused = backbone::mbhead_resolve(o, &c)) return refused;
-        const int64_t esz = c.x3 ? 4 : 2, nb = c.nb, ns = c.ns;
-        if (!need(o.in, true, "in", pin * o.Cin * esz) || !need(o.out, true, "out", pin * o.Cout * esz) || !need(o.w2, true, "w2", (int64_t)o.Cout * o.Cin * esz) ||
-            !need(o.bias2, true, "bias2", (int64_t)o.Cout * 4) || !need(o.w, true, "w", (int64_t)9 * o.Cout * 4) ||
-            !need(o.bias, true, "bias", (int64_t)o.Cout * 4) || !need(o.aux, true, "aux", (int64_t)o.B * nb * o.Cout * 4)) return why->c_str();
-        if (c.hpart && (!need(o.scale, true, "scale", (int64_t)o.aux0 * o.Cout * 4) || !need(o.out2, true, "out2", (int64_t)o.B * nb * ns * o.aux0 * 4))) return why->c_str();
-        if ((o.flags & backbone::BACKBONE_TIMELINE) && !need(o.in2, true, "in2", (int64_t)o.B * nb * ns * 256)) return why->c_str();      // phase timeline (tools/mbslice_bench.py)
-        return nullptr;
-    }
-    case FTC_OP_FMBCONV: {
-        backbone::FmbconvChoice c;
-        if (const char* refused = backbone::fmbconv_resolve(o, &c)) return refused;
-        const int64_t E = c.E, esz = c.x3 ? 4 : 2;      // (fp16x3 form: fp32 tensors, pre-split weights, out2 = the pre-split copy)
-        if (!need(o.in, true, "in", pin * o.Cin * esz) || !need(o.out, true, "out", pin * o.Cout * 4) || !need(o.w2, true, "w2", E * 9 * o.Cin * esz) ||
-            !need(o.bias2, true, "bias2", E * 4) || !need(o.w, true, "w", (int64_t)o.Cout * E * esz) || !need(o.bias, true, "bias", (int64_t)o.Cout * 4) ||
-            !need(o.in2, (o.flags & FTC_FLAG_RESIDUAL) != 0, "in2", pin * o.Cout * 4) || !need(o.out2, false, "out2", pin * o.Cout * esz)) return why->c_str();
-        return nullptr;
-    }
-    case FTC_OP_SE: {
-        backbone::SeChoice c;
-        if (const char* refused = backbone::se_resolve(o, &c)) return refused;
-        if (!need(o.aux, true, "aux", (int64_t)o.B * o.aux1 * (c.hpart ? o.aux0 : o.Cin) * 4) || !need(o.out, true, "out", (int64_t)o.B * o.Cin * 4) ||
-            !need(o.in2, true, "in2", (int64_t)o.B * o.aux0 * 4) || !need(o.w, !c.hpart, "w", (int64_t)o.aux0 * o.Cin * 4) ||
-            !need(o.w2, true, "w2", (int64_t)o.aux0 * o.Cin * 4) || !need(o.bias, true, "bias", (int64_t)o.aux0 * 4) ||
-            !need(o.bias2, true, "bias2", (int64_t)o.Cin * 4)) return why->c_str();
-        if (o.flags & FTC_FLAG_SE_FOLD) {
-            const int64_t eb = c.family == backbone::SE_FOLDX3 ? 4 : 2;
-            if (!need(o.in, true, "in", (int64_t)o.Cout_total * o.Cin * eb) || !need(o.out2, true, "out2", (int64_t)o.B * o.Cout_total * o.Cin * eb)) return why->c_str();
-        }
-        return nullptr;
-    }
-    case FTC_OP_UPCAT: {
-        backbone::UpcatChoice c;
-        if (const char* refused = backbone::upcat_resolve(o, &c)) return refused;
-        const int64_t cyt = o.Cin_total > 0 ? o.Cin_total : o.aux0;
-        const int64_t in_ext = ((o.flags & FTC_FLAG_GROUP_IN_SLICE) ? 1 : G) * pin * cyt * es(c.T);
-        if (!need(o.in, o.aux0 > 0, "in", in_ext) || !need(o.in2, true, "in2", pout * o.aux1 * es(c.TT)) ||
-            !need(o.out, true, "out", G * pout * (o.aux0 + o.aux1) * es(c.T)) || !need(o.scale, true, "scale", G * o.aux1 * 4) ||
-            !need(o.shift, true, "shift", G * o.aux1 * 4)) return why->c_str();
-        return nullptr;
-    }
-    case FTC_OP_TAPSUM:
-        if (o.aux0 <= 0 || o.aux1 <= 0) return "tapsum: bad aux0 / aux1";
-        if (!need(o.in, true, "in", G * pin * o.aux0 * 4) || !need(o.out, true, "out") || !need(o.w, true, "w", (int64_t)o.aux1 * 16) ||
-            !need(o.bias, true, "bias", (int64_t)o.aux1 * 4)) return why->c_str();
-        if (o.aux0 < 4 || o.aux0 > 32 || o.aux0 % 4 || o.aux1 < 1 || o.aux1 > 64 || o.Cout_total < 1 || o.groups < 1) return "tapsum: bad aux0 / aux1 / Cout_total / groups";
-        return nullptr;
-    case FTC_OP_BNSTAT: {
-        if (o.Cin <= 0) return "bnstat: Cin must be positive";
-        if (o.in_dtype != FTC_F32 && !ftc_is16(o.in_dtype)) return "bnstat: unknown dtype";
-        const int64_t M = pin;
-        if (!need(o.in, true, "in", M * o.Cin * es(o.in_dtype)) || !need(o.out, true, "out", (int64_t)4 * o.Cin * 4) || !need(o.w, true, "w", (int64_t)o.Cin * 4) ||
-            !need(o.bias, true, "bias", (int64_t)o.Cin * 4) || !need(o.aux, false, "aux", (int64_t)2 * o.Cin * 4) ||
-            !need(o.in2, true, "in2", (int64_t)ftc_bnstat_chunks(M) * 2 * o.Cin * 8)) return why->c_str();
-        return nullptr;
-    }
-    case FTC_OP_BNACT: {
-        if (o.Cin <= 0 || o.aux0 < 0 || o.aux0 > 65535) return "bnact: bad Cin / aux0";
-        if ((o.in_dtype != FTC_F32 && !ftc_is16(o.in_dtype)) || (o.out_dtype != FTC_F32 && !ftc_is16(o.out_dtype))) return "bnact: unknown dtype";
-        const int tc = o.w_dtype == FTC_F16 ? FTC_F16 : FTC_BF16;
-        if ((ftc_is16(o.in_dtype) && o.in_dtype != tc) || (ftc_is16(o.out_dtype) && o.out_dtype != tc)) return "bnact: 16-bit tensors must be in the plan's 16-bit type (w_dtype)";
-        if ((o.flags & FTC_FLAG_RESIDUAL) && o.res_dtype != FTC_F32 && o.res_dtype != tc) return "bnact: residual must be fp32 or the plan's 16-bit type";
-        if (o.act != FTC_ACT_NONE && o.act != FTC_ACT_SILU && o.act != FTC_ACT_GELU) return "bnact: unknown activation";
-        if (!need(o.in, true, "in", pin * o.Cin * es(o.in_dtype)) || !need(o.out, true, "out", pin * o.Cin * es(o.out_dtype)) ||
-            !need(o.scale, true, "scale", (int64_t)o.Cin * 4) || !need(o.shift, true, "shift", (int64_t)o.Cin * 4) ||
-            !need(o.in2, (o.flags & FTC_FLAG_RESIDUAL) != 0, "in2", pin * o.Cin * es(o.res_dtype)) || !need(o.w2, false, "w2", (int64_t)o.B * 4) ||
-            !need(o.out2, false, "out2", pin * o.Cin * 2) || !need(o.aux, false, "aux", (int64_t)o.B * (o.aux0 > 0 ? o.aux0 : 1) * o.Cin * 4)) return why->c_str();
-        if (o.out2.base != FTC_BASE_NULL && o.out_dtype != FTC_F32) return "bnact: out2 (16-bit copy) needs an fp32 primary output";
-        return nullptr;
-    }
-    case FTC_OP_NMS:
-        if (!need(o.out, true, "out")) return why->c_str();
-        if (o.Cout_total < 2) return "nms: heat-map needs >= 2 channels";
-        return nullptr;
-    case FTC_OP_GATHER_ROWS:
-        if (o.aux0 <= 0 || o.Cin <= 0 || (o.Cin & 3) || o.Cout_total < o.Cin || (o.Cout_total & 7)) return "gather_rows: need aux0 > 0, Cin % 4 == 0, Cout_total >= Cin, Cout_total % 8 == 0";
-        if (o.out_dtype != FTC_F32 && !ftc_is16(o.out_dtype)) return "gather_rows: unknown out_dtype";
-        if (!need(o.in, true, "in", pin * o.Cin * 4) || !need(o.in2, true, "in2", (int64_t)o.aux0 * 4) || !need(o.out, true, "out", (int64_t)o.aux0 * o.Cout_total * es(o.out_dtype))) return why->c_str();
-        return nullptr;
-    case FTC_OP_LOSSES:
-    case FTC_OP_LOSS_BWD: {
-        const int64_t hw = (int64_t)o.H * o.W;
-        if (!need(o.in, true, "in", pin * 9 * 4) || !need(o.in2, true, "in2", o.B * 5 * hw * 4) || !need(o.w, true, "w", o.B * 2 * hw * 4)) return why->c_str();
-        if (o.aux0 < 0) return "losses: aux0 (selected rows) must be >= 0";
-        if (o.aux0 > 0 && (!need(o.w2, true, "w2", (int64_t)o.aux0 * 1091 * 4) || !need(o.bias, true, "bias", (int64_t)o.aux0 * 1093 * 4) ||
-                           !need(o.bias2, true, "bias2", (int64_t)o.aux0 * 1097 * 4) || !need(o.scale, true, "scale", (int64_t)o.aux0 * 4))) return why->c_str();
-        if (o.kind == FTC_OP_LOSSES) {
-            if (!need(o.out, true, "out", 64) || !need(o.aux, true, "aux", ftc_losses_scratch_bytes())) return why->c_str();
-        } else {
-            if (!need(o.out, true, "out", pin * 9 * 4) || !need(o.shift, true, "shift", 36) || !need(o.aux, true, "aux", 64)) return why->c_str();
-            if (o.aux0 > 0 && (o.aux1 < 1097 || (o.aux1 & 3) || !need(o.out2, true, "out2", (int64_t)3 * o.aux0 * o.aux1 * 4))) return "loss_bwd: out2 / aux1 (padded logit row >= 1097, % 4 == 0)";
-        }
-        return nullptr;
-    }
-    case FTC_OP_SCATTER_ROWS:
-        if (o.aux0 <= 0 || o.Cout_total <= 0 || (o.Cout_total & 3)) return "scatter_rows: need aux0 > 0 and Cout_total % 4 == 0";
-        if (!need(o.in, true, "in", (int64_t)o.aux0 * o.Cout_total * 4) || !need(o.in2, true, "in2", (int64_t)o.aux0 * 4) || !need(o.out, true, "out", pin * o.Cout_total * 4)) return why->c_str();
-        return nullptr;
-    case FTC_OP_BNBWD: {
-        if (o.Cin <= 0 || (o.Cin & 3)) return "bnbwd: Cin must be a positive multiple of 4";
-        const int64_t gs = o.Cin_total > 0 ? o.Cin_total : o.Cin;
-        if ((gs & 3) || (o.cin_off & 3) || o.cin_off + o.Cin > gs) return "bnbwd: bad channel slice of the incoming gradient";
-        if (o.act != FTC_ACT_NONE && o.act != FTC_ACT_SILU && o.act != FTC_ACT_GELU) return "bnbwd: unknown activation";
-        if (o.out.base == FTC_BASE_NULL && o.out2.base == FTC_BASE_NULL) return "bnbwd: needs out (fp32) and / or out2 (16-bit copy)";
-        if (o.out2.base != FTC_BASE_NULL && !ftc_is16(o.w_dtype)) return "bnbwd: out2 is a 16-bit copy in the plan's compute type (w_dtype)";
-        if ((o.flags & FTC_FLAG_ACCUM) && o.out.base == FTC_BASE_NULL) return "bnbwd: FTC_FLAG_ACCUM adds onto out (fp32): it needs out, out2 alone has nothing to add to";
-        if (o.in_dtype != FTC_F32 && !(ftc_is16(o.in_dtype) && o.in_dtype == o.w_dtype)) return "bnbwd: in_dtype (the type z is stored in) is fp32 or the plan's 16-bit compute type (w_dtype)";
-        if (!need(o.in, true, "in", pin * gs * 4) || !need(o.in2, true, "in2", pin * o.Cin * es(o.in_dtype)) || !need(o.scale, true, "scale", (int64_t)4 * o.Cin * 4) ||
-            !need(o.out, false, "out", pin * o.Cin * 4) || !need(o.out2, false, "out2", pin * o.Cin * 2) || !need(o.w, false, "w", (int64_t)o.Cin * 4) || !need(o.shift, false, "shift", (int64_t)o.Cin * 4) ||
-            !need(o.w2, false, "w2", (int64_t)o.B * 4) || !need(o.bias, false, "bias", (int64_t)o.B * o.Cin * 4) || !need(o.bias2, false, "bias2", (int64_t)o.B * o.Cin * 4) ||
-            !need(o.aux, true, "aux", (int64_t)ftc_bnstat_chunks(pin) * 2 * o.Cin * 8 + (int64_t)2 * o.Cin * 4)) return why->c_str();
-        return nullptr;
-    }
-    case FTC_OP_WGRAD: {
-        // the op's form and its kernel choice (wgrad_choice.h) come first, as the form checks always did: a malformed op reports its form, not a missing buffer
-        wgradimpl::WgradChoice wc;
-        if (const char* refused = wgradimpl::wgrad_resolve(o, &wc)) return refused;
-        const int64_t cit = o.Cin_total > 0 ? o.Cin_total : o.Cin, cot = o.Cout_total > 0 ? o.Cout_total : o.Cout;
-        const int64_t kk = (int64_t)o.ksize * o.ksize;
-        if (!need(o.in, true, "in", pin * cit * es(o.in_dtype)) || !need(o.in2, true, "in2", pout * cot * es(o.res_dtype)) || !need(o.out, true, "out", kk * o.Cout * o.Cin * 4) ||
-            !need(o.aux, true, "aux", (int64_t)o.aux0 * kk * o.Cout * o.Cin * 4) || !need(o.scale, (o.flags & FTC_FLAG_SE_SCALE) != 0, "scale", (int64_t)o.B * o.Cin * 4)) return why->c_str();
-        return nullptr;
-    }
-    case FTC_OP_DWBWD:
-        if (o.Cin <= 0 || (o.Cin & 3) || (o.stride != 1 && o.stride != 2)) return "dwbwd: Cin % 4 == 0, stride 1 | 2";
-        if (o.Ho != (o.H - 1) / o.stride + 1 || o.Wo != (o.W - 1) / o.stride + 1) return "dwbwd: Ho/Wo inconsistent";
-        // data gradient (out; needs w) and weight gradient (out2 + aux; needs in) are each optional, at least one is there
-        if (o.out.base == FTC_BASE_NULL && o.out2.base == FTC_BASE_NULL) return "dwbwd: neither out (data gradient) nor out2 (weight gradient)";
-        if (!need(o.in2, true, "in2", pout * o.Cin * 4)) return why->c_str();
-        if (o.out.base != FTC_BASE_NULL && (!need(o.out, true, "out", pin * o.Cin * 4) || !need(o.w, true, "w", (int64_t)9 * o.Cin * 4))) return why->c_str();
-        if (o.out2.base != FTC_BASE_NULL && (!need(o.in, true, "in", pin * o.Cin * 4) || !need(o.out2, true, "out2", (int64_t)9 * o.Cin * 4) ||
-                                             !need(o.aux, true, "aux", (int64_t)ftc_chunks256(pout) * 9 * o.Cin * 8))) return why->c_str();
-        return nullptr;
-    case FTC_OP_SEBWD:
-        if (o.Cin <= 0 || (o.Cin & 3) || o.aux0 <= 0 || o.aux1 <= 0) return "sebwd: C (% 4 == 0), S, P must be positive";
-        if ((size_t)(2 * o.Cin + 2 * o.aux0) * 4 > 64000) return "sebwd: C / S too large for LDS";
-        if (!need(o.in, true, "in", pin * o.Cin * 4) || !need(o.in2, true, "in2", pin * o.Cin * 4) || !need(o.scale, true, "scale", (int64_t)o.B * o.Cin * 4) ||
-            !need(o.aux, true, "aux", (int64_t)o.B * o.aux1 * o.Cin * 4) || !need(o.w, true, "w", (int64_t)o.aux0 * o.Cin * 4) || !need(o.w2, true, "w2", (int64_t)o.aux0 * o.Cin * 4) ||
-            !need(o.bias, true, "bias", (int64_t)o.aux0 * 4) || !need(o.out, true, "out", ((int64_t)(4 + 32) * o.B * o.Cin + (int64_t)2 * o.B * o.aux0) * 4) ||
-            !need(o.out2, true, "out2", ((int64_t)2 * o.aux0 * o.Cin + o.aux0 + o.Cin) * 4)) return why->c_str();
-        return nullptr;
-    case FTC_OP_UPCATBWD:
-        if (o.aux0 <= 0 || (o.aux0 & 3) || o.Cin_total < o.aux0 || (o.Cin_total & 3) || o.Ho <= 0 || o.Wo <= 0) return "upcatbwd: bad channel counts";
-        if (!need(o.in, true, "in", pout * o.Cin_total * 4) || !need(o.out, true, "out", pin * o.aux0 * 4)) return why->c_str();
-        return nullptr;
-    case FTC_OP_DILATE:
-        if (o.Cin <= 0 || (o.Cin & 3) || o.Ho != 2 * o.H || o.Wo != 2 * o.W) return "dilate: Cin % 4 == 0, Ho = 2H, Wo = 2W";
-        if (!need(o.in, true, "in", pin * o.Cin * 4) || !need(o.out, true, "out", pout * o.Cin * 4)) return why->c_str();
-        return nullptr;
-    case FTC_OP_TOPDGRAD:
-        if (o.Cin <= 0 || o.Cin > 8 || o.Cout <= 0 || (o.Cout & 3) || o.cin_off + o.Cin > o.Cin_total) return "topdgrad: 1..8 gradient channels, Cout % 4 == 0";
-        if (!need(o.in, true, "in", pin * o.Cin_total * 4) || !need(o.w, true, "w", (int64_t)o.Cin * 9 * o.Cout * es(o.w_dtype)) || !need(o.out, true, "out", pin * o.Cout * 4)) return why->c_str();
-        return nullptr;
-    case FTC_OP_COLSUM: {
-        const int64_t ct = o.Cin_total > 0 ? o.Cin_total : o.Cin;
-        if (o.Cin <= 0 || o.cin_off + o.Cin > ct) return "colsum: bad column slice";
-        if (!need(o.in, true, "in", pin * ct * 4) || !need(o.out, true, "out", (int64_t)o.Cin * 4) || !need(o.aux, true, "aux", (int64_t)ftc_chunks256(pin) * o.Cin * 8)) return why->c_str();
-        return nullptr;
-    }
-    case FTC_OP_STEMWGRAD:
-        if (o.Cout <= 0 || o.Cout > 32 || o.Ho != (o.H - 1) / 2 + 1 || o.Wo != (o.W - 1) / 2 + 1) return "stemwgrad: Cout <= 32, Ho/Wo of a stride-2 3x3";
-        if (!need(o.in, true, "in") || !need(o.in2, true, "in2", pout * o.Cout * 4) || !need(o.out, true, "out", (int64_t)27 * o.Cout * 4) ||
-            !need(o.aux, true, "aux", (int64_t)ftc_stemwgrad_chunks(pout) * 27 * o.Cout * 8)) return why->c_str();
-        return nullptr;
-    case FTC_OP_FILL:
-        if (o.Cin <= 0) return "fill: Cin must be positive";
-        if (!need(o.out, true, "out", pin * o.Cin * 4)) return why->c_str();
-        return nullptr;
-    case FTC_OP_JOIN:
-        return nullptr;
-    default:
-        return "unknown op kind";
-    }
+    return nullptr;
 }
 
 inline void* resolve(const ftc_ref& r, void* const bases[FTC_NUM_BASES]) {
@@ -758,7 +543,16 @@ int ftc_wgrad_splits(int B, int Ho, int Wo, int Cout, int Cin, int ksize) {
     return ftc_wgrad_splits_impl(B, Ho, Wo, Cout, Cin, ksize);
 }
 
-int64_t ftc_losses_scratch_bytes(void) { return (int64_t)(512 * 9 + 512 * 4) * 8; }
+int ftc_op_extents(const ftc_op* op, int64_t bytes[FTC_NUM_OPERANDS], int32_t state[FTC_NUM_OPERANDS]) {
+    if (!op || !bytes || !state) return fail(FTC_ERR_INVALID, "ftc_op_extents: null arguments");
+    OpExtents e;
+    if (const char* refused = op_extents(*op, &e)) return fail(FTC_ERR_INVALID, std::string("ftc_op_extents: ") + refused);
+    std::memcpy(bytes, e.bytes, sizeof e.bytes);
+    std::memcpy(state, e.state, sizeof e.state);
+    return FTC_OK;
+}
+
+int64_t ftc_losses_scratch_bytes(void) { return FTC_LOSSES_SCRATCH_BYTES; }
 
 int ftc_losses(const float* heatmap, const int64_t heat_strides[4], const float* labelmap, const int32_t* idmap, int B, int h, int w,
                const float* dec0, const float* dec1, const float* dec2, const int32_t* sel_index, const int32_t* count, int64_t cap,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/ftc.h"
+#include "op_extents.h"      // host only: the operand extents of every op kind, the chunk counts the launchers share with them, conv_validate
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -213,13 +214,6 @@ hipError_t launch_bnstat(const OpArgs& a, hipStream_t s);
 hipError_t launch_bnact(const OpArgs& a, hipStream_t s);
 // fpn_ops.hip: 3x3 convolutions with 1..4 output channels on fp32 tensors (vector units; see thin_conv3x3_kernel, ftc_thin_conv_legal in conv_choice.h)
 hipError_t launch_thin_conv(const OpArgs& a, hipStream_t s);
-// FTC_OP_BNSTAT: number of row chunks the partial sums are split into
-// (64 rows per chunk up to 512 chunks: a 24x24-map layer has 4608 rows -- with 256-row chunks its partial pass was 200 workgroups of 64
-//  serial loads each, slower than the streaming it does)
-inline int ftc_bnstat_chunks(long M) { const long n = (M + 63) / 64; return (int)(n < 1 ? 1 : n > 512 ? 512 : n); }
-// row chunks of the depthwise weight-gradient and column-sum partial passes (256 rows each)
-inline int ftc_chunks256(long M) { const long n = (M + 255) / 256; return (int)(n < 1 ? 1 : n > 512 ? 512 : n); }
-inline int ftc_stemwgrad_chunks(long M) { const long n = (M + 255) / 256; return (int)(n < 1 ? 1 : n > 2048 ? 2048 : n); }
 // train step (bwd_ops.hip, wgrad.hip)
 hipError_t launch_bnbwd(const OpArgs& a, hipStream_t s);
 hipError_t launch_wgrad(const OpArgs& a, hipStream_t s);
@@ -243,5 +237,4 @@ hipError_t launch_fmbconv(const OpArgs& a, hipStream_t s);      // fused_mbconv.
 hipError_t launch_upcat(const OpArgs& a, hipStream_t s);
 hipError_t launch_nms(const OpArgs& a, hipStream_t s);
 hipError_t launch_tapsum(const OpArgs& a, hipStream_t s);
-const char* conv_validate(const ftc_op& op);   // NULL if supported, else reason
 void conv_kernel_label(const ftc_op& op, char* buf, int len);

@@ -9,6 +9,7 @@
 #include "../../include/ftc.h"
 #include "backbone_choice.h"
 #include "conv_choice.h"
+#include "op_extents.h"
 #include "wgrad_choice.h"
 
 struct ftc_plan {
@@ -23,9 +24,10 @@ int ftc_set_error(int code, const std::string& msg);
 // backbone_choice.h: the kernel choice of FTC_OP_STEM, DWCONV, SE, MBHEAD, FMBCONV and UPCAT (backbone::<kind>_resolve + <kind>_format_label) and the geometry
 // the plan builder asks before it emits an op (ftc_mbhead_legal, ftc_mbhead_band_rows, ftc_mbhead_bands, ftc_mbhead_slice, ftc_fmbconv_legal, ...)
 
-// conv_igemm.hip: NULL if the convolution op (incl. its tuned kernel choice ftc_op.aux0) is supported, else the reason
-// (conv_choice.h: the choice itself, and conv_pinned_choice / conv_small_tile_choice, which write one back into aux0)
-const char* conv_validate(const ftc_op& op);
+// conv_choice.h: the choice of a convolution op, conv_validate (NULL if the op, incl. its tuned kernel choice ftc_op.aux0, is supported, else the reason)
+// and conv_pinned_choice / conv_small_tile_choice, which write a choice back into aux0
+
+// op_extents.h: op_extents -- per operand of an op whether its form uses it and the bytes it spans, or the reason the form is refused
 
 // wgrad.hip: the kernel label of an FTC_OP_WGRAD op (wgrad_choice.h: wgrad_resolve + wgrad_format_label)
 void wgrad_kernel_label(const ftc_op& op, char* buf, int len);

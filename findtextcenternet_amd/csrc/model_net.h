@@ -132,6 +132,7 @@ struct PlanOptions {
     bool no_topfuse = false, no_topfuse32 = false;                                      // FTC_NO_TOPFUSE, FTC_NO_TOPFUSE32
     bool no_upfuse = false, no_upfuse32 = false, no_upfuse32_l2 = false;                // FTC_NO_UPFUSE, FTC_NO_UPFUSE32, FTC_NO_UPFUSE32_L2
     bool no_bnfold = false, no_bnfold32 = false, no_wl1 = false, no_tuning = false;     // FTC_NO_BNFOLD, FTC_NO_BNFOLD32, FTC_NO_WL1, FTC_NO_TUNING
+    int shrink_buf = -1;                                                                // FTC_PLAN_SHRINK_BUF (tests: that buffer is reserved 256 bytes short)
     auto operator<=>(const PlanOptions&) const = default;
 };
 // tuning_override: if given, receives the value of FTC_TUNING_OVERRIDE as it was at the first call in the process (or null)

@@ -98,6 +98,7 @@ PlanOptions read_plan_options(const char** tuning_override) {
     o.no_bnfold32 = on("FTC_NO_BNFOLD32");
     o.no_wl1 = on("FTC_NO_WL1");
     o.no_tuning = on("FTC_NO_TUNING");
+    if (const char* e = std::getenv("FTC_PLAN_SHRINK_BUF")) o.shrink_buf = *e ? std::atoi(e) : -1;
     // FTC_TUNING_OVERRIDE=<file of "signature aux0" lines>: entries replacing / extending the compiled-in table (tuning experiments without
     // a rebuild, e.g. tools/lanes_tuning.py: choices measured for the two-lane steady state instead of the kernel alone).  Not a member: read
     // once per process, for tuning_table.
@@ -193,6 +194,19 @@ private:
     static int esize(int dt) { return dt == FTC_F32 ? 4 : 2; }
     R buf(int64_t nelem, int dt) { bufs_.push_back({align_up(nelem * esize(dt))}); return {1, (int64_t)bufs_.size() - 1, 0}; }
     R sub(const R& b, int64_t off) const { return {1, b.v, b.extra + off}; }
+    // the op as op_extents reads it: the int fields, and which operands are given
+    static ftc_op form_of(const SymOp& s) {
+        ftc_op o = s.o;
+        for (int i = 0; i < FTC_NUM_OPERANDS; ++i) (&o.in)[i].base = (&s.in)[i] ? FTC_BASE_WORKSPACE : FTC_BASE_NULL;
+        return o;
+    }
+    // A pure scratch operand of the op being built (its int fields and the operands its form depends on are set): as many bytes as the op touches through it
+    R scratch(const SymOp& s, int operand) {
+        OpExtents e;
+        if (const char* refused = op_extents(form_of(s), &e)) { if (err_.empty()) err_ = refused; return {}; }
+        bufs_.push_back({align_up(e.bytes[operand])});
+        return {1, (int64_t)bufs_.size() - 1, 0};
+    }
     R wref(const std::string& name, int64_t off = 0) {
         auto it = m_->blob.table.find(name);
         if (it == m_->blob.table.end()) { if (err_.empty()) err_ = "packed weight '" + name + "' missing"; return {}; }
@@ -402,15 +416,15 @@ void Builder::emit_fmb_one(const BlockSpec& blk, const BlockPlan& d, R y, R yb) 
 void Builder::emit_mb_head(const BlockSpec& blk, const BlockPlan& d, R dw, R part) {
     const std::string p = blk.prefix + ".block";
     const int A = md_.act, h = d.h, w = d.w;
-    const R sums = buf((int64_t)B * d.nbands * blk.exp, FTC_F32);
     SymOp s = geom(FTC_OP_MBHEAD, h, w, d.ho, d.wo, blk.cin, blk.exp, 3, 1);
     ftc_op& o = s.o;
     o.act = FTC_ACT_SILU; o.in_dtype = A; o.out_dtype = A; o.w_dtype = A;
     o.Cout_total = d.mb_slice; o.aux0 = blk.squeeze; o.aux1 = d.band_rows;
     o.flags = (in_blocked_ ? FTC_FLAG_KBLOCK32 : 0) | md_.split | (d.presplit ? FTC_FLAG_PRESPLIT : 0);
     // (fp16x3: the head streams the PRE-SPLIT copy of its input)
-    s.in = md_.x3 ? xb_ : gin(); s.out = dw; s.w2 = wref(p + ".0.w"); s.bias2 = wref(p + ".0.b"); s.w = wref(p + ".1.w"); s.bias = wref(p + ".1.b"); s.aux = sums;
+    s.in = md_.x3 ? xb_ : gin(); s.out = dw; s.w2 = wref(p + ".0.w"); s.bias2 = wref(p + ".0.b"); s.w = wref(p + ".1.w"); s.bias = wref(p + ".1.b");
     s.scale = wref(p + ".2.w1"); s.out2 = part;
+    s.aux = scratch(s, OPD_AUX);                             // the per-band channel sums: written, read by nothing
     emit({p + ".0+1", "conv1x1+dw3x3", 2.0 * B * h * w * blk.exp * (blk.cin + 9),
           (double)B * h * w * (blk.cin + blk.exp) * esize(A) + (double)blk.exp * blk.cin * esize(A) + blk.exp * 44.0 + 4.0 * blk.exp * blk.squeeze}, s);
 }
@@ -432,14 +446,14 @@ void Builder::emit_se_project(const BlockSpec& blk, const BlockPlan& d, R dw, R 
     const std::string p = blk.prefix + ".block";
     const int A = md_.act, ho = d.ho, wo = d.wo;
     const bool slice = d.form == BlockForm::MB_SLICED, foldse = d.foldse;
-    const R sc = buf((int64_t)B * blk.exp, FTC_F32);
-    const R hid = buf((int64_t)B * blk.squeeze, FTC_F32);
     const int fdt = md_.dual ? A : FTC_F32;
-    const R wb = foldse ? buf((int64_t)B * blk.cout * blk.exp, fdt) : R();
     SymOp s = geom(FTC_OP_SE, ho, wo, 0, 0, blk.exp, blk.exp);
     ftc_op& o = s.o;
     o.flags = (foldse ? FTC_FLAG_SE_FOLD | (md_.dual ? 0 : FTC_FLAG_SPLIT16) : 0) | (slice ? FTC_FLAG_SE_HPART : 0); o.w_dtype = foldse ? fdt : 0;
     o.Cout_total = foldse ? blk.cout : 0; o.aux0 = blk.squeeze; o.aux1 = d.P;
+    const R sc = buf((int64_t)B * blk.exp, FTC_F32);
+    const R hid = scratch(s, OPD_IN2);                       // the hidden layer
+    const R wb = foldse ? buf((int64_t)B * blk.cout * blk.exp, fdt) : R();
     s.aux = part; s.out = sc; s.in2 = hid; s.w = wref(p + ".2.w1"); s.w2 = wref(p + ".2.w2t"); s.bias = wref(p + ".2.b1");
     s.bias2 = wref(p + ".2.b2"); s.in = foldse ? wref(p + ".3.w") : R(); s.out2 = wb;
     const double se_bytes = (slice ? 4.0 : 8.0) * blk.exp * blk.squeeze + (double)B * d.P * (slice ? blk.squeeze : blk.exp) * 4 +
@@ -692,6 +706,19 @@ int Builder::build_decoder(ModelPlan* out) {
 
 // liveness-based first-fit arena + resolution of the symbolic operands
 int Builder::finish(ModelPlan* out, int mh, int mw) {
+    if (opt_.shrink_buf >= 0 && opt_.shrink_buf < (int)bufs_.size()) bufs_[opt_.shrink_buf].nbytes -= ALIGN;      // (tests: the fit check below must refuse it)
+    // The arena places buffers side by side: an operand that runs past the buffer reserved for it would run into a live neighbour
+    for (size_t i = 0; i < ops_.size(); ++i) {
+        OpExtents e;
+        if (op_extents(form_of(ops_[i]), &e) != nullptr) continue;                       // (a refused form: plan validation reports it)
+        for (int j = 0; j < FTC_NUM_OPERANDS; ++j) {
+            const R& r = (&ops_[i].in)[j];
+            if (r.kind != 1 || e.state[j] == FTC_OPERAND_UNUSED || r.extra + e.bytes[j] <= bufs_[r.v].nbytes) continue;
+            return ftc_set_error(FTC_ERR_INVALID, "ftc model plan: op " + std::to_string(i) + " (" + meta_[i].name + "): operand " + kOperandName[j] + " spans " +
+                                                      std::to_string(e.bytes[j]) + " bytes from offset " + std::to_string(r.extra) + " of a buffer of " +
+                                                      std::to_string(bufs_[r.v].nbytes));
+        }
+    }
     std::vector<int> order(bufs_.size());
     for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bufs_[a].first < bufs_[b].first; });

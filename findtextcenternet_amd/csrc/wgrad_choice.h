@@ -86,7 +86,7 @@ inline int wgrad_splits(int B, int Ho, int Wo, int Cout, int Cin, int ksize) {
 }
 
 // The choice `o` runs with and NULL, or the reason the op is refused (the choice is then not filled).  What is checked here is the op's form; the extents of
-// its buffers are validate_op's.
+// its buffers are op_extents.h's.
 inline const char* wgrad_resolve(const ftc_op& o, WgradChoice* choice) {
     if (o.Cin <= 0 || o.Cout <= 0 || o.Ho <= 0 || o.Wo <= 0 || (o.ksize != 1 && o.ksize != 3) || (o.stride != 1 && o.stride != 2)) return "wgrad: bad sizes";
     if (o.w_dtype != FTC_F32 && !is16(o.w_dtype)) return "wgrad: unknown compute type";

@@ -75,19 +75,39 @@ class Builder:
         self.bufs.append(b)
         return ("ws", b, 0)
 
+    def scratch(self) -> tuple:
+        """A scratch operand of the op it is given to: emit() reserves what ftc_op_extents says that op touches through it."""
+        return ("scratch",)
+
     def w(self, name: str):
         return ("w", self.table[name])
 
     def g(self, name: str):
         return ("g", self.ptable[name])
 
-    def emit(self, _name: str = "", **f) -> None:
+    @staticmethod
+    def _fill(op, f: dict) -> None:
+        """The int fields of an emitted op into the ftc_op; every operand it carries marked as given."""
+        for k, v in f.items():
+            if k not in L.REFS:
+                setattr(op, k, int(v))
+            elif v is not None:
+                getattr(op, k).base = L.BASE_WORKSPACE
+
+    def emit(self, _name: str = "", **f) -> dict:
+        """Appends the op; returns its fields with every scratch() placeholder replaced by the buffer reserved for it."""
         idx = len(self.ops)
+        if ("scratch",) in f.values():
+            op = L.Op()
+            self._fill(op, f)
+            nbytes, _ = L.op_extents(op)
+            f = {k: self.buf(nbytes[L.REFS.index(k)]) if v == ("scratch",) else v for k, v in f.items()}
         for v in f.values():
             if isinstance(v, tuple) and v[0] == "ws":
                 v[1].first, v[1].last = min(v[1].first, idx), max(v[1].last, idx)
         self.ops.append(f)
         self.names.append(_name)
+        return f
 
     def join(self) -> None:
         """FTC_OP_JOIN: the main stream waits for the side stream; every buffer a pending side op touches lives until here."""
@@ -131,11 +151,9 @@ class Builder:
 
     def bnstat(self, z, h, w, c, bn_name, eps, B=None):
         B = B or self.B
-        M = B * h * w
-        nchunk = max(1, min(512, -(-M // 64)))
         ss = self.buf(4 * c * 4)                              # scale | shift | mean | 1/std (FTC_OP_BNSTAT)
         self.emit(bn_name, kind=L.OP_BNSTAT, in_dtype=getattr(z[1], "dt", L.F32), B=B, H=h, W=w, Cin=c, aux0=_fbits(eps), aux1=_fbits(0.1), in_=z, w=self.w(bn_name + ".weight"),
-                  bias=self.w(bn_name + ".bias"), aux=self.w(bn_name + ".running"), out=ss, in2=self.buf(nchunk * 2 * c * 8))
+                  bias=self.w(bn_name + ".bias"), aux=self.w(bn_name + ".running"), out=ss, in2=self.scratch())
         return ss
 
     def bn(self, z, h, w, c, bn_name, eps, act, residual=None, keep=None, sums_p=0, B=None, want32=True, want16=True):
@@ -163,14 +181,13 @@ class Builder:
         """-> (dz fp32 | None, dz 16-bit | None): dz of a convolution's BatchNorm is read by that convolution's two GEMMs only."""
         B = B or self.B
         M = B * h * w
-        nchunk = max(1, min(512, -(-M // 64)))
         want16 = want16 and self.h16 and out is None
         want32 = want32 or not want16 or out is not None
         d32 = out if out is not None else (self.buf(M * c * 4) if want32 else None)
         d16 = self.buf(M * c * 2) if want16 else None
         self.emit("bwd:" + bn_name, kind=L.OP_BNBWD, flags=L.FLAG_ACCUM if accum else 0, act=act, w_dtype=self.cdt, in_dtype=getattr(z[1], "dt", L.F32), B=B, H=h, W=w, Cin=c,
                   Cin_total=gy_total, cin_off=gy_off, in_=gy, in2=z, scale=ss, w2=keep, bias=ga, bias2=gb, out=d32, out2=d16,
-                  w=self.g(bn_name + ".weight"), shift=self.g(bn_name + ".bias"), aux=self.buf(nchunk * 2 * c * 8 + 2 * c * 4))
+                  w=self.g(bn_name + ".weight"), shift=self.g(bn_name + ".bias"), aux=self.scratch())
         return (d32, d16)
 
     def wgrad(self, x, dz, h, w, cin, cout, k, stride, wname, se=None, cin_total=0, cin_off=0, cout_total=0, cout_off=0, B=None):
@@ -191,7 +208,7 @@ class Builder:
             self.side_op()
         self.emit("wgrad:" + wname, kind=L.OP_WGRAD, flags=(L.FLAG_SE_SCALE if se is not None else 0) | (L.FLAG_SIDE_STREAM if self.side else 0), w_dtype=self.cdt, in_dtype=xdt, res_dtype=ddt, B=B, H=h,
                   W=w, Ho=ho, Wo=wo, Cin=cin, Cin_total=cin_total, cin_off=cin_off, Cout=cout, Cout_total=cout_total, cout_off=cout_off, ksize=k,
-                  stride=stride, aux0=S, in_=xin, in2=din, scale=se, out=self.g(wname), aux=self.buf(S * k * k * cout * cin * 4))
+                  stride=stride, aux0=S, in_=xin, in2=din, scale=se, out=self.g(wname), aux=self.scratch())
 
     def dgrad(self, dz, ho, wo, cout, wname, cin, k, stride, h, w, add=None, cout_pad=None, B=None):
         """d input fp32 [B,h,w,cin] of a convolution whose d output is dz = (fp32, 16-bit) [B,ho,wo,cout] (+ add)."""
@@ -229,21 +246,24 @@ class Builder:
             top = max(top, off + b.nbytes)
         ops = (L.Op * n_ops)()
         for i, f in enumerate(self.ops):
+            self._fill(ops[i], f)
+            nbytes, _ = L.op_extents(ops[i])
             for k, v in f.items():
-                if k in ("in_", "in2", "out", "w", "w2", "bias", "bias2", "scale", "shift", "aux", "out2"):
-                    if v is None:
-                        continue
-                    r = getattr(ops[i], k)
-                    if v[0] == "ws":
-                        r.base, r.offset = L.BASE_WORKSPACE, v[1].offset + v[2]
-                    elif v[0] == "w":
-                        r.base, r.offset = L.BASE_WEIGHTS, v[1]
-                    elif v[0] == "g":
-                        r.base, r.offset = L.BASE_GRADS, v[1]
-                    else:
-                        r.base, r.offset = L.BASE_INPUT, 0
+                if k not in L.REFS or v is None:
+                    continue
+                r = getattr(ops[i], k)
+                if v[0] == "ws":
+                    r.base, r.offset = L.BASE_WORKSPACE, v[1].offset + v[2]
+                    # the arena places buffers side by side: an operand that runs past the buffer reserved for it would run into a live neighbour
+                    if v[2] + nbytes[L.REFS.index(k)] > v[1].nbytes:
+                        raise RuntimeError(f"train plan: op {i} ({self.names[i]}): operand {k.rstrip('_')} spans {nbytes[L.REFS.index(k)]} bytes from offset "
+                                           f"{v[2]} of a buffer of {v[1].nbytes}")
+                elif v[0] == "w":
+                    r.base, r.offset = L.BASE_WEIGHTS, v[1]
+                elif v[0] == "g":
+                    r.base, r.offset = L.BASE_GRADS, v[1]
                 else:
-                    setattr(ops[i], k, int(v))
+                    r.base, r.offset = L.BASE_INPUT, 0
         return ops, top + 256
 
 
@@ -298,12 +318,12 @@ def emit_detector_forward(g: Builder, sh, B: int, H: int, W: int) -> dict:
                 pdw = -(-ho // th) * -(-wo // 8)
                 zd = g.buf(B * ho * wo * e * 4)
                 g.emit(b + ".1.0", kind=L.OP_DWCONV, act=L.ACT_NONE, in_dtype=L.F32, out_dtype=L.F32, B=B, H=h, W=w, Ho=ho, Wo=wo, Cin=e, Cout=e, ksize=3,
-                       stride=stride, aux0=pdw, in_=y0[0], out=zd, w=g.w(b + ".1.0.weight#dw"), bias=g.w("zeros"), aux=g.buf(B * pdw * e * 4))
+                       stride=stride, aux0=pdw, in_=y0[0], out=zd, w=g.w(b + ".1.0.weight#dw"), bias=g.w("zeros"), aux=g.scratch())
                 pse = max(1, min(16, (ho * wo) // 64))
                 y1, sums, ss1 = g.bn(zd, ho, wo, e, b + ".1.1", BACKBONE_EPS, L.ACT_SILU, sums_p=pse)                 # fp32 for the SE backward + copy
                 s = sh[b + ".2.fc1.weight"][0]
                 sc = g.buf(B * e * 4)
-                g.emit(b + ".2", kind=L.OP_SE, B=B, H=ho, W=wo, Cin=e, Cout=e, aux0=s, aux1=pse, aux=sums, out=sc, in2=g.buf(B * s * 4),
+                g.emit(b + ".2", kind=L.OP_SE, B=B, H=ho, W=wo, Cin=e, Cout=e, aux0=s, aux1=pse, aux=sums, out=sc, in2=g.scratch(),
                        w=g.w(b + ".2.fc1.weight"), w2=g.w(b + ".2.fc2.weight#t"), bias=g.w(b + ".2.fc1.bias"), bias2=g.w(b + ".2.fc2.bias"))
                 z3, _, _ = g.conv(y1, ho, wo, e, b + ".3.0.weight", cout, 1, se=sc)
                 x, _, ss3 = g.bn(z3, ho, wo, cout, b + ".3.1", BACKBONE_EPS, L.ACT_NONE, residual=residual, keep=keep)

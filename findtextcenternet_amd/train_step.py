@@ -248,7 +248,7 @@ class TrainStep:
         has_dec = len(dec) == 3
         g.emit("losses", kind=L.OP_LOSSES, B=B, H=mh, W=mw, aux0=n_rows if has_dec else 0, in_=maps, in2=lab, w=idm, w2=dec[0]["out"] if has_dec else None,
                bias=dec[1]["out"] if has_dec else None, bias2=dec[2]["out"] if has_dec else None, scale=sel if has_dec else None, out=lossv,
-               aux=g.buf(int(g.lib.ftc_losses_scratch_bytes())))
+               aux=g.scratch())
         n_fwd = len(g.ops)
         # ---------------- backward ----------------
         gmaps = g.buf(B * mh * mw * 9 * 4)
@@ -263,7 +263,7 @@ class TrainStep:
             for jb, d in enumerate(dec):
                 go = ("ws", gdec[1], jb * n_rows * DEC_PAD * 4)
                 g.emit("bwd:" + d["b"] + ".6.bias", kind=L.OP_COLSUM, B=1, H=n_rows, W=1, Cin=d["cout"], Cin_total=DEC_PAD, in_=go, out=g.g(d["b"] + ".6.bias"),
-                       aux=g.buf(max(1, min(512, -(-n_rows // 256))) * d["cout"] * 8))
+                       aux=g.scratch())
                 g.wgrad(d["x"], (go, None), n_rows, 1, d["cin"], d["cout"], 1, 1, d["b"] + ".6.weight", cout_total=DEC_PAD, B=1)
                 gy = g.dgrad((go, None), n_rows, 1, d["cout"], d["b"] + ".6.weight", d["cin"], 1, 1, n_rows, 1, cout_pad=DEC_PAD, B=1)
                 for li in (1, 0):
@@ -282,18 +282,17 @@ class TrainStep:
         # heads
         gtap = [g.buf(B * th_ * tw_ * tc * 4) for (_, tc, th_, tw_) in taps]
         tap_written = [False] * len(taps)
-        nchunk_m = max(1, min(512, -(-(B * mh * mw) // 256)))
         for hd in reversed(heads):
             hp, co, cy = hd["hp"], hd["co"], hd["cy"]
             wn = f"{hp}.top_conv.0.weight"
             if hd["ch"] is None:
                 g.emit("bwd:" + hp + ".top.bias", kind=L.OP_COLSUM, B=B, H=mh, W=mw, Cin=co, Cin_total=128, in_=gfeat, out=g.g(f"{hp}.top_conv.0.bias"),
-                       aux=g.buf(nchunk_m * co * 8))
+                       aux=g.scratch())
                 g.wgrad(hd["y"], (gfeat, None), mh, mw, cy, co, 3, 1, wn, cout_total=128)
                 gy = g.dgrad((gfeat, None), mh, mw, co, wn, cy, 3, 1, mh, mw, cout_pad=128)        # (_flatten pads the 100 feature channels to 128)
             else:
                 g.emit("bwd:" + hp + ".top.bias", kind=L.OP_COLSUM, B=B, H=mh, W=mw, Cin=co, Cin_total=9, cin_off=hd["ch"], in_=gmaps,
-                       out=g.g(f"{hp}.top_conv.0.bias"), aux=g.buf(nchunk_m * co * 8))
+                       out=g.g(f"{hp}.top_conv.0.bias"), aux=g.scratch())
                 g.wgrad(hd["y"], (gmaps, None), mh, mw, cy, co, 3, 1, wn, cout_total=9, cout_off=hd["ch"])
                 gy = g.buf(B * mh * mw * cy * 4)
                 g.emit("topdgrad:" + hp, kind=L.OP_TOPDGRAD, w_dtype=self.cdt, B=B, H=mh, W=mw, Cin=co, Cin_total=9, cin_off=hd["ch"], Cout=cy, in_=gmaps,
@@ -323,7 +322,7 @@ class TrainStep:
             if kind == "stem":
                 gz = g.bn_bwd(gx, rec["z"], rec["ss"], rec["h"], rec["w"], rec["c"], P + ".0.1", L.ACT_SILU, want32=True, want16=False)
                 g.emit("stemwgrad", kind=L.OP_STEMWGRAD, B=B, H=H, W=W, Ho=rec["h"], Wo=rec["w"], Cout=rec["c"], in_=("in",), in2=gz[0], out=g.g(P + ".0.0.weight"),
-                       aux=g.buf(max(1, min(2048, -(-(B * rec["h"] * rec["w"]) // 256))) * 27 * rec["c"] * 8))
+                       aux=g.scratch())
                 continue
             gout = gx
             b, h_, w_, c_, cout, stride, ho, wo = rec["b"], rec["h"], rec["w"], rec["c"], rec["cout"], rec["stride"], rec["ho"], rec["wo"]
@@ -336,22 +335,20 @@ class TrainStep:
                 g.wgrad(rec["y1"], gz3, ho, wo, e, cout, 1, 1, b + ".3.0.weight", se=rec["sc"])
                 gys = g.dgrad(gz3, ho, wo, cout, b + ".3.0.weight", e, 1, 1, ho, wo)
                 s = rec["s"]
-                scr = g.buf((36 * B * e + 2 * B * s) * 4)
-                g.emit("sebwd:" + b, kind=L.OP_SEBWD, B=B, H=ho, W=wo, Cin=e, aux0=s, aux1=rec["pse"], in_=gys, in2=rec["y1"][0], scale=rec["sc"], aux=rec["sums"],
-                       w=g.w(b + ".2.fc1.weight"), w2=g.w(b + ".2.fc2.weight#t"), bias=g.w(b + ".2.fc1.bias"), bias2=g.w(b + ".2.fc2.bias"), out=scr,
-                       out2=g.g(b + ".2.fc1.weight"))
+                scr = g.emit("sebwd:" + b, kind=L.OP_SEBWD, B=B, H=ho, W=wo, Cin=e, aux0=s, aux1=rec["pse"], in_=gys, in2=rec["y1"][0], scale=rec["sc"], aux=rec["sums"],
+                             w=g.w(b + ".2.fc1.weight"), w2=g.w(b + ".2.fc2.weight#t"), bias=g.w(b + ".2.fc1.bias"), bias2=g.w(b + ".2.fc2.bias"), out=g.scratch(),
+                             out2=g.g(b + ".2.fc1.weight"))["out"]
                 gzd = g.bn_bwd(gys, rec["zd"], rec["ss1"], ho, wo, e, b + ".1.1", L.ACT_SILU, ga=rec["sc"], gb=("ws", scr[1], 3 * B * e * 4), want32=True, want16=False)
                 gy0 = g.buf(B * h_ * w_ * e * 4)
-                dw_aux = g.buf(max(1, min(512, -(-(B * ho * wo) // 256))) * 9 * e * 8)
                 if g.side:
                     # the weight half on the side stream, like the dense weight gradients (nothing on the chain reads it); the data half stays
                     g.emit("dwbwd:" + b, kind=L.OP_DWBWD, B=B, H=h_, W=w_, Ho=ho, Wo=wo, Cin=e, stride=stride, in2=gzd[0], w=g.w(b + ".1.0.weight#dw"), out=gy0)
                     g.side_op()
                     g.emit("dwwgrad:" + b, kind=L.OP_DWBWD, flags=L.FLAG_SIDE_STREAM, B=B, H=h_, W=w_, Ho=ho, Wo=wo, Cin=e, stride=stride, in_=rec["y0"][0], in2=gzd[0],
-                           out2=g.g(b + ".1.0.weight"), aux=dw_aux)
+                           out2=g.g(b + ".1.0.weight"), aux=g.scratch())
                 else:
                     g.emit("dwbwd:" + b, kind=L.OP_DWBWD, B=B, H=h_, W=w_, Ho=ho, Wo=wo, Cin=e, stride=stride, in_=rec["y0"][0], in2=gzd[0], w=g.w(b + ".1.0.weight#dw"),
-                           out=gy0, out2=g.g(b + ".1.0.weight"), aux=dw_aux)
+                           out=gy0, out2=g.g(b + ".1.0.weight"), aux=g.scratch())
                 gz0 = g.bn_bwd(gy0, rec["z0"], rec["ss0"], h_, w_, e, b + ".0.1", L.ACT_SILU)
                 g.wgrad(rec["xin"], gz0, h_, w_, c_, e, 1, 1, b + ".0.0.weight")
                 gx = g.dgrad(gz0, h_, w_, e, b + ".0.0.weight", c_, 1, 1, h_, w_, add=skip)
@@ -611,31 +608,11 @@ class TrainStep:
 
     @staticmethod
     def _grad_write_extents(op) -> list:
-        """[(first element, one past the last)] of the flat gradient buffer an op writes: the FULL extent of every FTC_BASE_GRADS operand
-        (a parameter may straddle a bucket boundary, and FTC_OP_SEBWD writes four consecutive parameters through one operand)."""
-        k = op.kind
-        sizes = {}
-        if k == L.OP_WGRAD:
-            sizes["out"] = op.Cout * op.Cin * op.ksize * op.ksize
-        elif k == L.OP_BNBWD:
-            sizes["w"] = sizes["shift"] = op.Cin
-        elif k == L.OP_DWBWD:
-            sizes["out2"] = 9 * op.Cin
-        elif k == L.OP_SEBWD:
-            sizes["out2"] = 2 * op.aux0 * op.Cin + op.aux0 + op.Cin       # fc1.weight [S][C], fc1.bias [S], fc2.weight [C][S], fc2.bias [C]
-        elif k == L.OP_COLSUM:
-            sizes["out"] = op.Cin
-        elif k == L.OP_STEMWGRAD:
-            sizes["out"] = op.Cout * 27
-        ext = []
-        for f in ("in_", "in2", "out", "out2", "w", "w2", "bias", "bias2", "scale", "shift", "aux"):
-            r = getattr(op, f)
-            if r.base != L.BASE_GRADS:
-                continue
-            if f not in sizes:
-                raise RuntimeError(f"train plan: op kind {k} touches the gradient buffer through '{f}', whose extent _bucket_segments does not know")
-            ext.append((r.offset // 4, r.offset // 4 + int(sizes[f])))
-        return ext
+        """[(first element, one past the last)] of the flat gradient buffer an op writes: the FULL extent (ftc_op_extents) of every FTC_BASE_GRADS
+        operand (a parameter may straddle a bucket boundary, and FTC_OP_SEBWD writes four consecutive parameters through one operand)."""
+        nbytes, _ = L.op_extents(op)
+        refs = [(getattr(op, f), n) for f, n in zip(L.REFS, nbytes)]
+        return [(r.offset // 4, (r.offset + n) // 4) for r, n in refs if r.base == L.BASE_GRADS]
 
     def _bucket_segments(self, plan: dict) -> list:
         """[(first_op, last_op, bucket index)]: the backward ops in order, cut after the last op that writes into each bucket.

@@ -42,8 +42,9 @@ extern "C" {
       ftc_page_merge_variant (the demo script's selection + two-pass seed rows)
    10: FTC_OP_FMBCONV (Fused-MBConv block with expansion in one launch: 3x3 expand + SiLU + 1x1 project + residual)
    11: glyph code-point decode: ftc_glyph_select, ftc_glyph_decode_workspace_bytes, ftc_glyph_decode
-   12: ftc_conv_signature, ftc_tune_ops (the measured kernel selection of ftc_forward's plans, for a caller's own op array) */
-#define FTC_ABI_VERSION 12
+   12: ftc_conv_signature, ftc_tune_ops (the measured kernel selection of ftc_forward's plans, for a caller's own op array)
+   13: ftc_op_extents, FTC_NUM_OPERANDS, ftc_operand_state: what an op reads and writes through each of its operands */
+#define FTC_ABI_VERSION 13
 
 typedef enum ftc_status {
     FTC_OK = 0,
@@ -625,6 +626,19 @@ int ftc_pack_train_weights(const ftc_pack_entry* entries_dev, int n_entries, int
 
 /* Pixel splits FTC_OP_WGRAD should use for a layer (fills the GPU without oversizing the partial-sum scratch). */
 int ftc_wgrad_splits(int B, int Ho, int Wo, int Cout, int Cin, int ksize);
+
+/* What `op` reads or writes through each of its eleven operands, in the order of the ftc_refs in ftc_op -- in, in2, out, w, w2, bias, bias2, scale, shift,
+   aux, out2: state[i] says whether the op's form uses the operand at all, bytes[i] how many bytes it spans from the operand's start (0 = unknown:
+   ftc_plan_create checks only the start).  These are the numbers ftc_plan_create holds every operand to, so a caller that sizes a scratch operand
+   (FTC_OP_BNSTAT in2, FTC_OP_WGRAD aux, ...) by bytes[i] cannot undersize it.  Reads only the op's int fields and which operands are given (base !=
+   FTC_BASE_NULL): no plan, no GPU.  FTC_ERR_INVALID with the reason in ftc_last_error for an op whose form ftc_plan_create would refuse. */
+#define FTC_NUM_OPERANDS 11
+typedef enum ftc_operand_state {
+    FTC_OPERAND_UNUSED = 0,    /* not examined, given or not */
+    FTC_OPERAND_OPTIONAL = 1,  /* used when given */
+    FTC_OPERAND_REQUIRED = 2
+} ftc_operand_state;
+int ftc_op_extents(const ftc_op* op, int64_t bytes[FTC_NUM_OPERANDS], int32_t state[FTC_NUM_OPERANDS]);
 
 #ifdef __cplusplus
 }

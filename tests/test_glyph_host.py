@@ -66,7 +66,7 @@ def test_library_exports_glyph_entry_points():
     lib = L.load()
     for name in ("ftc_glyph_select", "ftc_glyph_decode", "ftc_glyph_decode_workspace_bytes"):
         assert name in L.EXPORTS and getattr(lib, name) is not None
-    assert lib.ftc_abi_version() == L.FTC_ABI_VERSION == 12
+    assert lib.ftc_abi_version() == L.FTC_ABI_VERSION == 13
 
 
 def test_glyph_select_rejects_bad_arguments_without_a_device():

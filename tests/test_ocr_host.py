@@ -106,7 +106,7 @@ def test_every_ocr_symbol_of_the_header_is_exported_and_bound():
     for s in declared:
         assert getattr(lib, s) is not None
     assert lib.ftc_ocr_abi_version() == 1
-    assert lib.ftc_text_abi_version() == 1 and lib.ftc_abi_version() == 12       # the two older surfaces are not touched
+    assert lib.ftc_text_abi_version() == 1 and lib.ftc_abi_version() == 13       # the two older surfaces are not touched
     assert not set(L.OCR_EXPORTS) & (set(L.EXPORTS) | set(L.TEXT_EXPORTS))
     # host-side refusals need no GPU: nothing is enqueued
     assert lib.ftc_ocr_assemble(None, 0, 99, None, 0, None, 1, 3, None, None) == -1 and b"feature_dim" in lib.ftc_last_error()

@@ -173,7 +173,7 @@ def test_every_symbol_of_the_compact_header_is_exported_and_bound():
     for s in declared:
         assert getattr(lib, s) is not None
     assert lib.ftc_text_compact_abi_version() == 1
-    assert lib.ftc_text_abi_version() == 1 and lib.ftc_ocr_abi_version() == 1 and lib.ftc_abi_version() == 12      # the three older surfaces
+    assert lib.ftc_text_abi_version() == 1 and lib.ftc_ocr_abi_version() == 1 and lib.ftc_abi_version() == 13      # the three older surfaces
     assert not set(L.TEXT_COMPACT_EXPORTS) & (set(L.EXPORTS) | set(L.TEXT_EXPORTS) | set(L.OCR_EXPORTS))
     # host-side refusals need no GPU: nothing is enqueued
     one = 16

@@ -75,7 +75,7 @@ def test_prep_header_declares_exactly_the_exported_set():
     for sym in L.PREP_EXPORTS:
         getattr(lib, sym)
     assert lib.ftc_prep_abi_version() == 1
-    assert lib.ftc_abi_version() == 12 and lib.ftc_text_abi_version() == 1 and lib.ftc_text_compact_abi_version() == 1 and lib.ftc_ocr_abi_version() == 1
+    assert lib.ftc_abi_version() == 13 and lib.ftc_text_abi_version() == 1 and lib.ftc_text_compact_abi_version() == 1 and lib.ftc_ocr_abi_version() == 1
     assert not set(L.PREP_EXPORTS) & (set(L.EXPORTS) | set(L.TEXT_EXPORTS) | set(L.TEXT_COMPACT_EXPORTS) | set(L.OCR_EXPORTS))
     # refused on the host: nothing is enqueued
     assert lib.ftc_page_ink(None, 1, None, 8, 8, 0.4, None, None, None) == -1 and b"null" in lib.ftc_last_error()

@@ -78,7 +78,7 @@ def test_sample_header_declares_exactly_the_exported_set():
     for sym in L.SAMPLE_EXPORTS:
         getattr(lib, sym)
     assert lib.ftc_sample_abi_version() == 1
-    assert lib.ftc_abi_version() == 12 and lib.ftc_text_abi_version() == 1 and lib.ftc_text_compact_abi_version() == 1
+    assert lib.ftc_abi_version() == 13 and lib.ftc_text_abi_version() == 1 and lib.ftc_text_compact_abi_version() == 1
     assert lib.ftc_ocr_abi_version() == 1 and lib.ftc_prep_abi_version() == 1
     assert not set(L.SAMPLE_EXPORTS) & (set(L.EXPORTS) | set(L.TEXT_EXPORTS) | set(L.TEXT_COMPACT_EXPORTS) | set(L.OCR_EXPORTS) | set(L.PREP_EXPORTS))
     # the mirrored record: 280 bytes, the fields where the header puts them
