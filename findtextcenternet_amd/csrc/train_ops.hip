@@ -14,8 +14,12 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t orderable(float v) {          // larger float <=> larger unsigned key
-    const uint32_t u = __float_as_uint(v);
+// larger float <=> larger unsigned key, with the two classes a comparison sort cannot tell apart folded onto one key each, as the reference's
+// stable descending sort treats them: -0.0 ties with +0.0, and every NaN (either sign, any payload) is one tie group above +inf
+__device__ __forceinline__ uint32_t orderable(float v) {
+    const uint32_t u = __float_as_uint(v), mag = u & 0x7fffffffu;
+    if (mag > 0x7f800000u) return 0xff800001u;                    // NaN: one above the key of +inf (0xff800000)
+    if (mag == 0u) return 0x80000000u;                            // +-0: the key of +0
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -280,7 +284,10 @@ __global__ void finish_losses_kernel(const double* __restrict__ map_partial, int
 
 // CoVWeightingLoss.forward (loss_func.py:24-72) for n <= 16 losses; state = [mean_L, mean_l, S_l, std_l][16] floats + alphas[16].
 // (The reference's `if not self.train:` tests a bound method and is never true: the weighted form is used in validation too.)
+// Contraction is off in this function alone: the reference rounds every product before it adds (separate float32 tensor ops), and a fused
+// mp * mean + omp * l, S += a * b or loss += alpha * L differs from that in the last bit (tests/step_operands.py cov_model is the statement).
 __global__ void cov_step_kernel(const float* __restrict__ L, int n, int iter, float* __restrict__ state, float* __restrict__ out_loss) {
+#pragma clang fp contract(off)
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float* mean_L = state; float* mean_l = state + 16; float* S_l = state + 32; float* std_l = state + 48; float* alphas = state + 64;
     float l[16];

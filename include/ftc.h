@@ -541,12 +541,14 @@ int ftc_page_merge_variant(const float* locations, const int32_t* order, int n_b
 
 /* TextDetectorModel.get_fmask (models/detector.py:270-281): mask[i] = 1 for the k largest of values[0..n) (ties at the k-th value:
    lowest index first, as the reference's stable sort), sel_index[0..k) = the selected indices ascending (= row order of `x[mask]`),
-   count[0] = number selected (min(k, n)).  sel_index / count may be NULL. */
+   count[0] = number selected (min(k, n)).  sel_index / count may be NULL.  As in that sort, -0.0 and +0.0 are one tie group, and every
+   NaN (either sign) is one tie group that ranks above +inf. */
 int ftc_topk_mask(const float* values, int64_t n, int64_t k, unsigned char* mask, int32_t* sel_index, int32_t* count, void* stream);
 /* Index list of an arbitrary boolean mask (`features[fmask]`, models/detector.py:265-266): sel_index[0..min(count, cap)) ascending. */
 int ftc_mask_compact(const unsigned char* mask, int64_t n, int32_t* sel_index, int64_t cap, int32_t* count, void* stream);
 /* rows[i][0..C) = features[sel_index[i]][0..C), zero-padded to c_pad columns (c_pad % 8 == 0), for i < min(count, cap); rows at and
-   beyond count are zero.  features = the NHWC block [P, C] fp32 the detector wrote; rows in `out_dtype` (FTC_F32 | FTC_BF16). */
+   beyond count are zero.  features = the NHWC block [P, C] fp32 the detector wrote; rows in `out_dtype` (FTC_F32 | FTC_BF16 | FTC_F16; rounded to
+   nearest even, fp16 saturating at +-65504 as every fp16 activation store).  count == NULL selects all `cap` rows. */
 int ftc_gather_rows(const float* features, const int32_t* sel_index, const int32_t* count, int64_t cap, int C, int c_pad, void* rows,
                     int out_dtype, void* stream);
 /* SimpleDecoder.forward in eval mode (models/detector.py:232-254): three MLPs 100 -> 2048 -> 2048 -> {1091, 1093, 1097} with
