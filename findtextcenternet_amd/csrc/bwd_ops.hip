@@ -229,12 +229,6 @@ __global__ __launch_bounds__(256) void bnbwd_apply_kernel(BnBwdP p, const float*
     }
 }
 
-inline int pick_quads(int C) {
-    const int q = C / 4;
-    for (int t : {64, 32, 16, 8, 4, 2}) if (q % t == 0) return t;
-    return 1;
-}
-
 // ------------------------------------------------------------------------------------------------------------------------
 // FTC_OP_DWBWD: depthwise 3x3 (pad 1, stride 1|2) backward.  32-bit index arithmetic throughout (validated: < 2^31 quads).
 // ------------------------------------------------------------------------------------------------------------------------
@@ -395,9 +389,8 @@ __global__ __launch_bounds__(256) void dwbwd_weight_final_kernel(const double* _
 
 // ------------------------------------------------------------------------------------------------------------------------
 // FTC_OP_SEBWD: y*s with s = sigmoid(fc2(SiLU(fc1(mean_hw y)))).  Scratch layout (floats): ds [B][C] | du2 [B][C] | mean [B][C] |
-// dmean/HW [B][C] | da1 [B][S] | h [B][S] | ds partial sums [B][SE_PCH][C].
+// dmean/HW [B][C] | da1 [B][S] | h [B][S] | ds partial sums [B][SE_PCH][C] (train_choice.h states it for the host side).
 // ------------------------------------------------------------------------------------------------------------------------
-constexpr int SE_PCH = 32;
 
 template <int Q>
 __global__ __launch_bounds__(256) void sebwd_ds_kernel(const float* __restrict__ g, const float* __restrict__ y, float* __restrict__ dsp, int HW, int C, int pch) {
@@ -808,7 +801,7 @@ __global__ __launch_bounds__(256) void pack_train_kernel(const ftc_pack_entry* _
     }
 }
 
-inline int nblocks(long total, int cap = 16384) { const long nb = (total + 255) / 256; return (int)(nb < 1 ? 1 : nb > cap ? cap : nb); }
+inline int nblocks(long total, int cap = 16384) { return (int)train::clamp_blocks(total, cap); }
 
 }  // namespace
 
@@ -820,127 +813,96 @@ hipError_t launch_pack_train(const ftc_pack_entry* entries, int n, long max_elem
 }
 
 namespace {
-template <int Q, bool FAST, typename TC, typename ZT>
-hipError_t bnbwd_run(const BnBwdP& p, double* part, float* coef, float* ggamma, float* gbeta, float* out, TC* out2, int accum, int nchunk, hipStream_t s) {
-    const dim3 grid(p.C / (4 * Q), nchunk);
-    hipLaunchKernelGGL((bnbwd_partial_kernel<Q, FAST, ZT>), grid, dim3(256), 0, s, p, part, nchunk);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bnbwd_final_kernel, dim3((p.C + 15) / 16), dim3(256), 0, s, part, ggamma, gbeta, coef, (long)p.M, p.C, nchunk);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    // the apply pass streams: enough row chunks to fill the GPU (the partial pass is bound to the scratch layout's chunk count)
-    int ach = (int)((4096L * 4 * Q) / p.C);
-    ach = ach < 1 ? 1 : ach > p.M / 8 + 1 ? p.M / 8 + 1 : ach;
-    hipLaunchKernelGGL((bnbwd_apply_kernel<Q, FAST, TC, ZT>), dim3(p.C / (4 * Q), ach), dim3(256), 0, s, p, coef, out, out2, accum, ach);
-    return hipGetLastError();
-}
 template <bool FAST, typename TC, typename ZT>
-hipError_t bnbwd_q(int q, const BnBwdP& p, double* part, float* coef, float* gg, float* gb, float* out, TC* out2, int accum, int nchunk, hipStream_t s) {
-    switch (q) {
-    case 64: return bnbwd_run<64, FAST, TC, ZT>(p, part, coef, gg, gb, out, out2, accum, nchunk, s);
-    case 32: return bnbwd_run<32, FAST, TC, ZT>(p, part, coef, gg, gb, out, out2, accum, nchunk, s);
-    case 16: return bnbwd_run<16, FAST, TC, ZT>(p, part, coef, gg, gb, out, out2, accum, nchunk, s);
-    case 8: return bnbwd_run<8, FAST, TC, ZT>(p, part, coef, gg, gb, out, out2, accum, nchunk, s);
-    case 4: return bnbwd_run<4, FAST, TC, ZT>(p, part, coef, gg, gb, out, out2, accum, nchunk, s);
-    case 2: return bnbwd_run<2, FAST, TC, ZT>(p, part, coef, gg, gb, out, out2, accum, nchunk, s);
-    default: return bnbwd_run<1, FAST, TC, ZT>(p, part, coef, gg, gb, out, out2, accum, nchunk, s);
-    }
+hipError_t bnbwd_run(const OpArgs& a, const train::BnbwdChoice& c, hipStream_t s) {
+    const ftc_op& o = *a.op;
+    BnBwdP p;
+    p.gy = (const float*)a.in; p.gs = c.gs; p.goff = o.cin_off;
+    p.z = a.in2; p.ss = a.scale; p.keep = (const float*)a.w2; p.ga = a.bias; p.gb = a.bias2;
+    p.HW = o.H * o.W; p.M = (int)c.M; p.C = o.Cin; p.act = o.act;
+    double* part = reinterpret_cast<double*>(a.aux);
+    float* coef = reinterpret_cast<float*>(part + (long)c.nchunk * 2 * p.C);
+    float* gg = (float*)const_cast<void*>(a.w);
+    float* gb = const_cast<float*>(a.shift);
+    return train::with_quads(c.Q, [&](auto q) {
+        constexpr int Q = decltype(q)::value;
+        hipLaunchKernelGGL((bnbwd_partial_kernel<Q, FAST, ZT>), dim3(c.partial_grid[0], c.partial_grid[1]), dim3(256), 0, s, p, part, c.nchunk);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(bnbwd_final_kernel, dim3(c.final_grid), dim3(256), 0, s, part, gg, gb, coef, c.M, p.C, c.nchunk);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((bnbwd_apply_kernel<Q, FAST, TC, ZT>), dim3(c.apply_grid[0], c.apply_grid[1]), dim3(256), 0, s, p, coef, (float*)a.out, (TC*)a.out2, c.accum, c.ach);
+        return hipGetLastError();
+    });
 }
 }  // namespace
 
 hipError_t launch_bnbwd(const OpArgs& a, hipStream_t s) {
-    const ftc_op& o = *a.op;
-    BnBwdP p;
-    p.gy = (const float*)a.in; p.gs = o.Cin_total > 0 ? o.Cin_total : o.Cin; p.goff = o.cin_off;
-    p.z = a.in2; p.ss = a.scale; p.keep = (const float*)a.w2; p.ga = a.bias; p.gb = a.bias2;
-    p.HW = o.H * o.W; p.M = o.B * o.H * o.W; p.C = o.Cin; p.act = o.act;
-    const int nchunk = ftc_bnstat_chunks(p.M);
-    double* part = reinterpret_cast<double*>(a.aux);
-    float* coef = reinterpret_cast<float*>(part + (long)nchunk * 2 * p.C);
-    const int q = pick_quads(p.C);
-    float* gg = (float*)const_cast<void*>(a.w);
-    float* gb = const_cast<float*>(a.shift);
-    const int accum = (o.flags & FTC_FLAG_ACCUM) ? 1 : 0;
-    // in_dtype = the type z (in2) is STORED in: fp32, or the plan's 16-bit compute type (what the reference's autocast stores: the
+    train::BnbwdChoice c;
+    if (train::bnbwd_resolve(*a.op, &c) != nullptr) return hipErrorInvalidValue;      // (plan creation refuses such ops)
+    // ZT = the type z (in2) is STORED in: fp32, or the plan's 16-bit compute type (what the reference's autocast stores: the
     // convolution wrote it in 16 bits, and the three BatchNorm passes -- statistics, normalise, backward -- stream half the bytes)
-    const bool z16 = ftc_is16(o.in_dtype);
-    if (o.w_dtype == FTC_F32) return bnbwd_q<false, float, float>(q, p, part, coef, gg, gb, (float*)a.out, (float*)nullptr, accum, nchunk, s);
-    if (o.w_dtype == FTC_F16)
-        return z16 ? bnbwd_q<true, _Float16, _Float16>(q, p, part, coef, gg, gb, (float*)a.out, (_Float16*)a.out2, accum, nchunk, s)
-                   : bnbwd_q<true, _Float16, float>(q, p, part, coef, gg, gb, (float*)a.out, (_Float16*)a.out2, accum, nchunk, s);
-    return z16 ? bnbwd_q<true, __bf16, __bf16>(q, p, part, coef, gg, gb, (float*)a.out, (__bf16*)a.out2, accum, nchunk, s)
-               : bnbwd_q<true, __bf16, float>(q, p, part, coef, gg, gb, (float*)a.out, (__bf16*)a.out2, accum, nchunk, s);
+    const bool z16 = c.zt != FTC_F32;
+    if (c.tc == FTC_F32) return bnbwd_run<false, float, float>(a, c, s);      // (no 16-bit copy: plan creation refuses out2)
+    if (c.tc == FTC_F16) return z16 ? bnbwd_run<true, _Float16, _Float16>(a, c, s) : bnbwd_run<true, _Float16, float>(a, c, s);
+    return z16 ? bnbwd_run<true, __bf16, __bf16>(a, c, s) : bnbwd_run<true, __bf16, float>(a, c, s);
 }
 
 hipError_t launch_dwbwd(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
-    const long M = (long)o.B * o.Ho * o.Wo;
-    const int nchunk = ftc_chunks256(M), C = o.Cin;
-    // `out` (data gradient) and `out2` + `aux` (weight gradient) are each optional (round 4): the train plan emits the weight half as its own op on
-    // the side stream -- nothing on the backward chain reads a depthwise weight gradient (7.4 ms of the step's main stream)
-    hipError_t e = hipSuccess;
-    if (a.out) {
-        static const bool old_form = [] { const char* e2 = std::getenv("FTC_DWBWD_DATA_OLD"); return e2 && *e2 && *e2 != '0'; }();
-        const long Mi = (long)o.B * o.H * o.W;
-        if (!old_form && Mi < 0x7fffffffL) {
-            const int Qd = pick_quads(C);
-            const int RLd = 256 / Qd;
-            // row chunks: ~8 workgroups per CU over all channel groups, at least 2 trips of 2 pixels per lane
-            long want = (2048L * 4 * Qd) / C;
-            const long maxc = Mi / (4L * RLd) + 1;
-            want = want < 1 ? 1 : want > maxc ? maxc : want;
-            const dim3 gd(C / (4 * Qd), (unsigned)want);
-#define DWD(QQ) hipLaunchKernelGGL(dwbwd_data_q_kernel<QQ>, gd, dim3(256), 0, s, (const float*)a.in2, (const float*)a.w, (float*)a.out, o.B, o.H, o.W, o.Ho, o.Wo, C, \
-                                   o.stride, (int)want)
-            switch (Qd) { case 64: DWD(64); break; case 32: DWD(32); break; case 16: DWD(16); break; case 8: DWD(8); break; case 4: DWD(4); break; case 2: DWD(2); break;
-                          default: DWD(1); }
-#undef DWD
-        } else
-        hipLaunchKernelGGL(dwbwd_data_kernel, dim3(nblocks((long)o.B * o.H * o.W * (C / 4))), dim3(256), 0, s, (const float*)a.in2, (const float*)a.w, (float*)a.out,
-                           o.B, o.H, o.W, o.Ho, o.Wo, C, o.stride);
-        e = hipGetLastError();
+    train::DwbwdChoice c;
+    if (train::dwbwd_resolve(o, &c) != nullptr) return hipErrorInvalidValue;      // (plan creation refuses such ops)
+    const int C = o.Cin;
+    const float* dz = (const float*)a.in2;
+    if (c.data.present) {
+        const dim3 grid(c.data.grid[0], c.data.grid[1]);
+        if (c.data.family == train::DW_Q)
+            train::with_quads(c.data.Q, [&](auto q) {
+                hipLaunchKernelGGL(dwbwd_data_q_kernel<decltype(q)::value>, grid, dim3(256), 0, s, dz, (const float*)a.w, (float*)a.out, o.B, o.H, o.W, o.Ho, o.Wo, C, o.stride,
+                                   c.data.want);
+            });
+        else
+            hipLaunchKernelGGL(dwbwd_data_kernel, grid, dim3(256), 0, s, dz, (const float*)a.w, (float*)a.out, o.B, o.H, o.W, o.Ho, o.Wo, C, o.stride);
+        hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    if (!a.out2) return hipSuccess;
+    if (!c.weight.present) return hipSuccess;
     double* part = reinterpret_cast<double*>(a.aux);
-    const int Q = pick_quads(C) > 16 ? 16 : pick_quads(C);        // 9 x 4 accumulators per lane: keep the LDS image at 36 KB
-#define DWW(QQ) hipLaunchKernelGGL(dwbwd_weight_partial_kernel<QQ>, dim3(C / (4 * QQ), nchunk), dim3(256), 0, s, (const float*)a.in, (const float*)a.in2, part, \
-                                   o.B, o.H, o.W, o.Ho, o.Wo, C, o.stride, nchunk)
-    switch (Q) { case 16: DWW(16); break; case 8: DWW(8); break; case 4: DWW(4); break; case 2: DWW(2); break; default: DWW(1); }
-#undef DWW
-    e = hipGetLastError();
+    train::with_quads<16>(c.weight.Q, [&](auto q) {
+        hipLaunchKernelGGL(dwbwd_weight_partial_kernel<decltype(q)::value>, dim3(c.weight.grid[0], c.weight.grid[1]), dim3(256), 0, s, (const float*)a.in, dz, part, o.B, o.H, o.W,
+                           o.Ho, o.Wo, C, o.stride, c.weight.nchunk);
+    });
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dwbwd_weight_final_kernel, dim3((9 * C + 255) / 256), dim3(256), 0, s, part, (float*)a.out2, C, nchunk);
+    hipLaunchKernelGGL(dwbwd_weight_final_kernel, dim3(c.weight.final_grid), dim3(256), 0, s, part, (float*)a.out2, C, c.weight.nchunk);
     return hipGetLastError();
 }
 
 hipError_t launch_sebwd(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
+    train::SebwdChoice c;
+    if (train::sebwd_resolve(o, &c) != nullptr) return hipErrorInvalidValue;      // (plan creation refuses such ops)
     const int C = o.Cin, S = o.aux0, P = o.aux1, HW = o.H * o.W;
     float* scratch = (float*)a.out;
-    float* dsp = scratch + (long)4 * o.B * C + (long)2 * o.B * S;
-    const int Q = pick_quads(C);
-    int pch = 1024 / ((C / (4 * Q)) * o.B);
-    pch = pch < 1 ? 1 : pch > SE_PCH ? SE_PCH : pch;
-    if (pch > HW / 16) pch = HW / 16 > 0 ? HW / 16 : 1;
-#define SEDS(QQ) hipLaunchKernelGGL(sebwd_ds_kernel<QQ>, dim3(C / (4 * QQ), pch, o.B), dim3(256), 0, s, (const float*)a.in, (const float*)a.in2, dsp, HW, C, pch)
-    switch (Q) { case 64: SEDS(64); break; case 32: SEDS(32); break; case 16: SEDS(16); break; case 8: SEDS(8); break; case 4: SEDS(4); break;
-                 case 2: SEDS(2); break; default: SEDS(1); }
-#undef SEDS
+    float* dsp = scratch + c.dsp_offset;
+    train::with_quads(c.Q, [&](auto q) {
+        hipLaunchKernelGGL(sebwd_ds_kernel<decltype(q)::value>, dim3(c.ds_grid[0], c.ds_grid[1], c.ds_grid[2]), dim3(256), 0, s, (const float*)a.in, (const float*)a.in2, dsp, HW, C,
+                           c.pch);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const float inv_hw = 1.0f / (float)HW;
-    hipLaunchKernelGGL(sebwd_prep_kernel, dim3((C + 255) / 256, o.B), dim3(256), 0, s, (const float*)a.aux, a.scale, scratch, o.B, C, S, P, inv_hw, pch);
+    hipLaunchKernelGGL(sebwd_prep_kernel, dim3(c.prep_grid[0], c.prep_grid[1]), dim3(256), 0, s, (const float*)a.aux, a.scale, scratch, o.B, C, S, P, inv_hw, c.pch);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sebwd_hidden_kernel, dim3((S + 3) / 4, o.B), dim3(256), 0, s, (const float*)a.w, a.bias, (const float*)a.w2, scratch, o.B, C, S);
+    hipLaunchKernelGGL(sebwd_hidden_kernel, dim3(c.hidden_grid[0], c.hidden_grid[1]), dim3(256), 0, s, (const float*)a.w, a.bias, (const float*)a.w2, scratch, o.B, C, S);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sebwd_dmean_kernel, dim3((C + 255) / 256, o.B), dim3(256), (size_t)S * sizeof(float), s, (const float*)a.w, scratch, o.B, C, S, inv_hw);
+    hipLaunchKernelGGL(sebwd_dmean_kernel, dim3(c.dmean_grid[0], c.dmean_grid[1]), dim3(256), (size_t)c.dmean_lds_bytes, s, (const float*)a.w, scratch, o.B, C, S, inv_hw);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sebwd_w_kernel, dim3((C + 255) / 256, S), dim3(256), 0, s, scratch, (float*)a.out2, o.B, C, S);
+    hipLaunchKernelGGL(sebwd_w_kernel, dim3(c.w_grid[0], c.w_grid[1]), dim3(256), 0, s, scratch, (float*)a.out2, o.B, C, S);
     return hipGetLastError();
 }
 

@@ -310,29 +310,9 @@ int ftc_plan_run_streams(const ftc_plan* plan, void* const bases[FTC_NUM_BASES],
 int ftc_op_kernel_label(const ftc_op* op, char* buf, int len) {
     if (!op || !buf || len <= 0) return fail(FTC_ERR_INVALID, "ftc_op_kernel_label: null arguments");
     if (backbone::format_label(*op, buf, len)) return FTC_OK;      // STEM, DWCONV, SE, MBHEAD, FMBCONV, UPCAT: formatted from the choice (backbone_choice.h)
-    switch (op->kind) {
-    case FTC_OP_CONV: conv_kernel_label(*op, buf, len); break;
-    case FTC_OP_NMS: std::snprintf(buf, len, "nms_kernel"); break;
-    case FTC_OP_TAPSUM: std::snprintf(buf, len, "tapsum_kernel"); break;
-    case FTC_OP_BNSTAT: std::snprintf(buf, len, "bnstat_partial+final<%s>", ftc_dtname(op->in_dtype)); break;
-    case FTC_OP_BNACT: std::snprintf(buf, len, "bnact_kernel<%s,%s>", ftc_dtname(op->in_dtype), ftc_dtname(op->out_dtype)); break;
-    case FTC_OP_GATHER_ROWS: std::snprintf(buf, len, "gather_rows_kernel"); break;
-    case FTC_OP_LOSSES: std::snprintf(buf, len, "map_loss+id_loss+finish"); break;
-    case FTC_OP_LOSS_BWD: std::snprintf(buf, len, "maploss_bwd+idloss_bwd"); break;
-    case FTC_OP_SCATTER_ROWS: std::snprintf(buf, len, "scatter_rows_kernel"); break;
-    case FTC_OP_BNBWD: std::snprintf(buf, len, "bnbwd_partial+final+apply"); break;
-    case FTC_OP_WGRAD: wgrad_kernel_label(*op, buf, len); break;
-    case FTC_OP_DWBWD: std::snprintf(buf, len, "dwbwd_data+weight<s%d>", op->stride); break;
-    case FTC_OP_SEBWD: std::snprintf(buf, len, "sebwd_ds+mlp+w"); break;
-    case FTC_OP_UPCATBWD: std::snprintf(buf, len, "upcatbwd_kernel"); break;
-    case FTC_OP_DILATE: std::snprintf(buf, len, "dilate_kernel"); break;
-    case FTC_OP_TOPDGRAD: std::snprintf(buf, len, "topdgrad_kernel<%s>", ftc_dtname(op->w_dtype)); break;
-    case FTC_OP_COLSUM: std::snprintf(buf, len, "colsum_partial+final"); break;
-    case FTC_OP_STEMWGRAD: std::snprintf(buf, len, "stemwgrad_partial+final"); break;
-    case FTC_OP_FILL: std::snprintf(buf, len, "memset"); break;
-    case FTC_OP_JOIN: std::snprintf(buf, len, "join"); break;
-    default: return fail(FTC_ERR_INVALID, "ftc_op_kernel_label: unknown op kind");
-    }
+    if (op->kind == FTC_OP_CONV) conv_kernel_label(*op, buf, len);
+    else if (op->kind == FTC_OP_WGRAD) wgrad_kernel_label(*op, buf, len);
+    else if (!train::format_label(*op, buf, len)) return fail(FTC_ERR_INVALID, "ftc_op_kernel_label: unknown op kind");      // every other kind (train_choice.h)
     return FTC_OK;
 }
 

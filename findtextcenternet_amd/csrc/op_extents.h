@@ -1,9 +1,9 @@
 // The operand extents of every op kind, stated in ONE place: op_extents() turns an ftc_op into, for each of its eleven operands, whether the op's form
 // uses it (unused | optional | required) and how many bytes it reads or writes from the operand's start -- or the reason the op's form is refused.
 // validate_op (plan creation: every operand inside its base), ftc_op_extents (the train-graph builder sizes its scratch operands and finds the gradient
-// floats an op writes from it) and both plan builders (every operand inside the buffer reserved for it) consume that one result, and the launchers read
-// the chunk counts below; tests/golden/op_extents.json.gz pins it, tests/c_abi/op_extents_host.cc prints it.
-// Host only: ftc.h, the three choice headers and the standard library, no HIP header and no kernel -- a plain C++ program can include it.  It reads an
+// floats an op writes from it) and both plan builders (every operand inside the buffer reserved for it) consume that one result;
+// tests/golden/op_extents.json.gz pins it, tests/c_abi/op_extents_host.cc prints it.  (The chunk counts the launchers share with it are train_choice.h's.)
+// Host only: ftc.h, the four choice headers and the standard library, no HIP header and no kernel -- a plain C++ program can include it.  It reads an
 // op's int fields and WHICH operands are given, never where they are.
 #pragma once
 #include <cstddef>
@@ -12,16 +12,9 @@
 #include "../../include/ftc.h"
 #include "backbone_choice.h"
 #include "conv_choice.h"
+#include "train_choice.h"
 #include "wgrad_choice.h"
 
-// ---- chunk counts a launcher shares with the table ------------------------------------------------------------------------------------------------
-// FTC_OP_BNSTAT / FTC_OP_BNBWD: number of row chunks the partial sums are split into
-// (64 rows per chunk up to 512 chunks: a 24x24-map layer has 4608 rows -- with 256-row chunks its partial pass was 200 workgroups of 64
-//  serial loads each, slower than the streaming it does)
-inline int ftc_bnstat_chunks(long M) { const long n = (M + 63) / 64; return (int)(n < 1 ? 1 : n > 512 ? 512 : n); }
-// row chunks of the depthwise weight-gradient and column-sum partial passes (256 rows each)
-inline int ftc_chunks256(long M) { const long n = (M + 255) / 256; return (int)(n < 1 ? 1 : n > 512 ? 512 : n); }
-inline int ftc_stemwgrad_chunks(long M) { const long n = (M + 255) / 256; return (int)(n < 1 ? 1 : n > 2048 ? 2048 : n); }
 // ftc_losses_scratch_bytes(): 512 partial rows of the nine map losses and of the four id losses, float64
 constexpr int64_t FTC_LOSSES_SCRATCH_BYTES = (int64_t)(512 * 9 + 512 * 4) * 8;
 
@@ -39,15 +32,14 @@ struct OpExtents {
     void opt(int i, int64_t b = 0) { set(i, false, b); }
 };
 
-// NULL and the table, or the reason the op's FORM is refused (the six backbone kinds and WGRAD: their resolver's; CONV: conv_validate's).
+// NULL and the table, or the reason the op's FORM is refused (the six backbone kinds, the five of train_choice.h and WGRAD: their resolver's; CONV: conv_validate's).
 inline const char* op_extents(const ftc_op& o, OpExtents* extents) {
     using backbone::given;
     using backbone::is16;
     OpExtents& e = *extents = OpExtents();
     auto es = [](int dt) -> int64_t { return dt == FTC_F32 ? 4 : 2; };
     auto known = [](int dt) { return dt == FTC_F32 || is16(dt); };
-    auto act_known = [](int act) { return act == FTC_ACT_NONE || act == FTC_ACT_SILU || act == FTC_ACT_GELU; };
-    if (o.B <= 0 || o.H <= 0 || o.W <= 0) return "B/H/W must be positive";
+    if (const char* refused = train::map_refusal(o)) return refused;
     const int64_t G = o.groups > 1 ? o.groups : 1, B = o.B, C = o.Cin, S = o.aux0;
     const int64_t pin = B * o.H * o.W, pout = B * o.Ho * o.Wo;
     switch (o.kind) {
@@ -133,23 +125,19 @@ inline const char* op_extents(const ftc_op& o, OpExtents* extents) {
         if (o.aux0 < 4 || o.aux0 > 32 || o.aux0 % 4 || o.aux1 < 1 || o.aux1 > 64 || o.Cout_total < 1 || o.groups < 1) return "tapsum: bad aux0 / aux1 / Cout_total / groups";
         e.req(OPD_IN, G * pin * o.aux0 * 4); e.req(OPD_OUT); e.req(OPD_W, (int64_t)o.aux1 * 16); e.req(OPD_BIAS, (int64_t)o.aux1 * 4);
         return nullptr;
-    case FTC_OP_BNSTAT:
-        if (o.Cin <= 0) return "bnstat: Cin must be positive";
-        if (!known(o.in_dtype)) return "bnstat: unknown dtype";
-        e.req(OPD_IN, pin * C * es(o.in_dtype)); e.req(OPD_OUT, 4 * C * 4); e.req(OPD_W, C * 4); e.req(OPD_BIAS, C * 4); e.opt(OPD_AUX, 2 * C * 4);
-        e.req(OPD_IN2, (int64_t)ftc_bnstat_chunks(pin) * 2 * C * 8);      // per-chunk float64 (sum, sum of squares)
+    case FTC_OP_BNSTAT: {
+        train::BnstatChoice c;
+        if (const char* refused = train::bnstat_resolve(o, &c)) return refused;
+        e.req(OPD_IN, pin * C * es(c.dtype)); e.req(OPD_OUT, 4 * C * 4); e.req(OPD_W, C * 4); e.req(OPD_BIAS, C * 4); e.opt(OPD_AUX, 2 * C * 4);
+        e.req(OPD_IN2, (int64_t)c.nchunk * 2 * C * 8);      // per-chunk float64 (sum, sum of squares)
         return nullptr;
+    }
     case FTC_OP_BNACT: {
-        if (o.Cin <= 0 || o.aux0 < 0 || o.aux0 > 65535) return "bnact: bad Cin / aux0";
-        if (!known(o.in_dtype) || !known(o.out_dtype)) return "bnact: unknown dtype";
-        const int tc = o.w_dtype == FTC_F16 ? FTC_F16 : FTC_BF16;
-        if ((is16(o.in_dtype) && o.in_dtype != tc) || (is16(o.out_dtype) && o.out_dtype != tc)) return "bnact: 16-bit tensors must be in the plan's 16-bit type (w_dtype)";
-        if ((o.flags & FTC_FLAG_RESIDUAL) && o.res_dtype != FTC_F32 && o.res_dtype != tc) return "bnact: residual must be fp32 or the plan's 16-bit type";
-        if (!act_known(o.act)) return "bnact: unknown activation";
-        if (given(o.out2) && o.out_dtype != FTC_F32) return "bnact: out2 (16-bit copy) needs an fp32 primary output";
-        e.req(OPD_IN, pin * C * es(o.in_dtype)); e.req(OPD_OUT, pin * C * es(o.out_dtype)); e.req(OPD_SCALE, C * 4); e.req(OPD_SHIFT, C * 4);
-        e.set(OPD_IN2, (o.flags & FTC_FLAG_RESIDUAL) != 0, pin * C * es(o.res_dtype)); e.opt(OPD_W2, B * 4); e.opt(OPD_OUT2, pin * C * 2);
-        e.opt(OPD_AUX, B * (o.aux0 > 0 ? o.aux0 : 1) * C * 4);
+        train::BnactChoice c;
+        if (const char* refused = train::bnact_resolve(o, &c)) return refused;
+        e.req(OPD_IN, pin * C * es(c.ti)); e.req(OPD_OUT, pin * C * es(c.to)); e.req(OPD_SCALE, C * 4); e.req(OPD_SHIFT, C * 4);
+        e.set(OPD_IN2, c.has_res, pin * C * es(o.res_dtype)); e.opt(OPD_W2, B * 4); e.opt(OPD_OUT2, pin * C * 2);
+        e.opt(OPD_AUX, B * c.P * C * 4);
         return nullptr;
     }
     case FTC_OP_NMS:
@@ -181,17 +169,11 @@ inline const char* op_extents(const ftc_op& o, OpExtents* extents) {
         e.req(OPD_IN, S * o.Cout_total * 4); e.req(OPD_IN2, S * 4); e.req(OPD_OUT, pin * o.Cout_total * 4);
         return nullptr;
     case FTC_OP_BNBWD: {
-        if (o.Cin <= 0 || (o.Cin & 3)) return "bnbwd: Cin must be a positive multiple of 4";
-        const int64_t gs = o.Cin_total > 0 ? o.Cin_total : o.Cin;
-        if ((gs & 3) || (o.cin_off & 3) || o.cin_off + o.Cin > gs) return "bnbwd: bad channel slice of the incoming gradient";
-        if (!act_known(o.act)) return "bnbwd: unknown activation";
-        if (!given(o.out) && !given(o.out2)) return "bnbwd: needs out (fp32) and / or out2 (16-bit copy)";
-        if (given(o.out2) && !is16(o.w_dtype)) return "bnbwd: out2 is a 16-bit copy in the plan's compute type (w_dtype)";
-        if ((o.flags & FTC_FLAG_ACCUM) && !given(o.out)) return "bnbwd: FTC_FLAG_ACCUM adds onto out (fp32): it needs out, out2 alone has nothing to add to";
-        if (o.in_dtype != FTC_F32 && !(is16(o.in_dtype) && o.in_dtype == o.w_dtype)) return "bnbwd: in_dtype (the type z is stored in) is fp32 or the plan's 16-bit compute type (w_dtype)";
-        e.req(OPD_IN, pin * gs * 4); e.req(OPD_IN2, pin * C * es(o.in_dtype)); e.req(OPD_SCALE, 4 * C * 4); e.opt(OPD_OUT, pin * C * 4); e.opt(OPD_OUT2, pin * C * 2);
+        train::BnbwdChoice c;
+        if (const char* refused = train::bnbwd_resolve(o, &c)) return refused;
+        e.req(OPD_IN, pin * c.gs * 4); e.req(OPD_IN2, pin * C * es(c.zt)); e.req(OPD_SCALE, 4 * C * 4); e.opt(OPD_OUT, pin * C * 4); e.opt(OPD_OUT2, pin * C * 2);
         e.opt(OPD_W, C * 4); e.opt(OPD_SHIFT, C * 4); e.opt(OPD_W2, B * 4); e.opt(OPD_BIAS, B * C * 4); e.opt(OPD_BIAS2, B * C * 4);
-        e.req(OPD_AUX, (int64_t)ftc_bnstat_chunks(pin) * 2 * C * 8 + 2 * C * 4);      // per-chunk float64 (sum dy, sum dy * xhat), then the two reduced rows
+        e.req(OPD_AUX, (int64_t)c.nchunk * 2 * C * 8 + 2 * C * 4);      // per-chunk float64 (sum dy, sum dy * xhat), then the two reduced rows
         return nullptr;
     }
     case FTC_OP_WGRAD: {
@@ -204,23 +186,23 @@ inline const char* op_extents(const ftc_op& o, OpExtents* extents) {
         e.set(OPD_SCALE, (o.flags & FTC_FLAG_SE_SCALE) != 0, B * C * 4);
         return nullptr;
     }
-    case FTC_OP_DWBWD:
-        if (o.Cin <= 0 || (o.Cin & 3) || (o.stride != 1 && o.stride != 2)) return "dwbwd: Cin % 4 == 0, stride 1 | 2";
-        if (o.Ho != (o.H - 1) / o.stride + 1 || o.Wo != (o.W - 1) / o.stride + 1) return "dwbwd: Ho/Wo inconsistent";
-        // data gradient (out; needs w) and weight gradient (out2 + aux; needs in) are each optional, at least one is there
-        if (!given(o.out) && !given(o.out2)) return "dwbwd: neither out (data gradient) nor out2 (weight gradient)";
+    case FTC_OP_DWBWD: {
+        train::DwbwdChoice c;
+        if (const char* refused = train::dwbwd_resolve(o, &c)) return refused;
         e.req(OPD_IN2, pout * C * 4); e.opt(OPD_OUT, pin * C * 4); e.opt(OPD_OUT2, 9 * C * 4);
-        if (given(o.out)) e.req(OPD_W, 9 * C * 4);
-        if (given(o.out2)) { e.req(OPD_IN, pin * C * 4); e.req(OPD_AUX, (int64_t)ftc_chunks256(pout) * 9 * C * 8); }
+        if (c.data.present) e.req(OPD_W, 9 * C * 4);
+        if (c.weight.present) { e.req(OPD_IN, pin * C * 4); e.req(OPD_AUX, (int64_t)c.weight.nchunk * 9 * C * 8); }
         return nullptr;
-    case FTC_OP_SEBWD:
-        if (o.Cin <= 0 || (o.Cin & 3) || o.aux0 <= 0 || o.aux1 <= 0) return "sebwd: C (% 4 == 0), S, P must be positive";
-        if ((size_t)(2 * o.Cin + 2 * o.aux0) * 4 > 64000) return "sebwd: C / S too large for LDS";
+    }
+    case FTC_OP_SEBWD: {
+        train::SebwdChoice c;
+        if (const char* refused = train::sebwd_resolve(o, &c)) return refused;
         e.req(OPD_IN, pin * C * 4); e.req(OPD_IN2, pin * C * 4); e.req(OPD_SCALE, B * C * 4); e.req(OPD_AUX, B * o.aux1 * C * 4); e.req(OPD_W, S * C * 4);
         e.req(OPD_W2, S * C * 4); e.req(OPD_BIAS, S * 4);
-        e.req(OPD_OUT, ((4 + 32) * B * C + 2 * B * S) * 4);                  // scratch: [4 + 32][B][C] and [2][B][S] fp32
+        e.req(OPD_OUT, train::sebwd_scratch_floats(B, C, S) * 4);           // scratch: [4][B][C], [2][B][S] and [SE_PCH][B][C] fp32
         e.req(OPD_OUT2, (2 * S * C + S + C) * 4);                           // fc1.weight [S][C], fc1.bias [S], fc2.weight [C][S], fc2.bias [C]
         return nullptr;
+    }
     case FTC_OP_UPCATBWD:
         if (o.aux0 <= 0 || (o.aux0 & 3) || o.Cin_total < o.aux0 || (o.Cin_total & 3) || o.Ho <= 0 || o.Wo <= 0) return "upcatbwd: bad channel counts";
         e.req(OPD_IN, pout * o.Cin_total * 4); e.req(OPD_OUT, pin * S * 4);

@@ -523,69 +523,54 @@ __global__ __launch_bounds__(256) void bnact_q_kernel(const TI* __restrict__ x, 
 
 hipError_t launch_bnstat(const OpArgs& a, hipStream_t s) {
     const ftc_op& o = *a.op;
-    const long M = (long)o.B * o.H * o.W;
-    const int C = o.Cin, nchunk = ftc_bnstat_chunks(M);
+    train::BnstatChoice c;
+    if (train::bnstat_resolve(o, &c) != nullptr) return hipErrorInvalidValue;      // (plan creation refuses such ops)
+    const int C = o.Cin, nchunk = c.nchunk;
     double* part = reinterpret_cast<double*>(const_cast<void*>(a.in2));
     float eps, mom;
     memcpy(&eps, &o.aux0, 4);
     memcpy(&mom, &o.aux1, 4);
-    const dim3 grid((C + 63) / 64, nchunk);
-    if (o.in_dtype == FTC_F32 && C % 4 == 0 && M < 0x7fffffffL) {
-        const int q = C / 4;
-        const int Q = q % 64 == 0 ? 64 : q % 32 == 0 ? 32 : q % 16 == 0 ? 16 : q % 8 == 0 ? 8 : q % 4 == 0 ? 4 : q % 2 == 0 ? 2 : 1;
-        const dim3 gq(C / (4 * Q), nchunk);
-#define BNSTAT_Q(QQ) hipLaunchKernelGGL(bnstat_partial_q_kernel<QQ>, gq, dim3(256), 0, s, (const float*)a.in, part, (int)M, C, nchunk)
-        switch (Q) { case 64: BNSTAT_Q(64); break; case 32: BNSTAT_Q(32); break; case 16: BNSTAT_Q(16); break; case 8: BNSTAT_Q(8); break;
-                     case 4: BNSTAT_Q(4); break; case 2: BNSTAT_Q(2); break; default: BNSTAT_Q(1); }
-#undef BNSTAT_Q
-    }
-    else if (o.in_dtype == FTC_F32) hipLaunchKernelGGL(bnstat_partial_kernel<float>, grid, dim3(256), 0, s, (const float*)a.in, part, M, C, nchunk);
-    else if (o.in_dtype == FTC_F16) hipLaunchKernelGGL(bnstat_partial_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)a.in, part, M, C, nchunk);
-    else hipLaunchKernelGGL(bnstat_partial_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)a.in, part, M, C, nchunk);
+    const dim3 grid(c.grid[0], c.grid[1]);
+    if (c.family == train::BN_Q)
+        train::with_quads(c.Q, [&](auto q) { hipLaunchKernelGGL(bnstat_partial_q_kernel<decltype(q)::value>, grid, dim3(256), 0, s, (const float*)a.in, part, (int)c.M, C, nchunk); });
+    else if (c.dtype == FTC_F32) hipLaunchKernelGGL(bnstat_partial_kernel<float>, grid, dim3(256), 0, s, (const float*)a.in, part, c.M, C, nchunk);
+    else if (c.dtype == FTC_F16) hipLaunchKernelGGL(bnstat_partial_kernel<_Float16>, grid, dim3(256), 0, s, (const _Float16*)a.in, part, c.M, C, nchunk);
+    else hipLaunchKernelGGL(bnstat_partial_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)a.in, part, c.M, C, nchunk);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bnstat_final_kernel, dim3((C + 15) / 16), dim3(256), 0, s, part, (const float*)a.w, a.bias, a.aux, (float*)a.out, M, C, nchunk, eps, mom);
+    hipLaunchKernelGGL(bnstat_final_kernel, dim3(c.final_grid), dim3(256), 0, s, part, (const float*)a.w, a.bias, a.aux, (float*)a.out, c.M, C, nchunk, eps, mom);
     return hipGetLastError();
 }
 
 namespace {
 template <typename TI, typename TO, typename TC>
-hipError_t launch_bnact_t(const OpArgs& a, hipStream_t s) {
+hipError_t launch_bnact_t(const OpArgs& a, const train::BnactChoice& c, hipStream_t s) {
     const ftc_op& o = *a.op;
-    const int HW = o.H * o.W, C = o.Cin, P = o.aux0 > 0 ? o.aux0 : 1;
-    const bool has_res = (o.flags & FTC_FLAG_RESIDUAL) != 0;
-    static const bool scalar_only = [] { const char* e = std::getenv("FTC_BNACT_SCALAR"); return e && *e && *e != '0'; }();
-    if (C % 4 == 0 && !scalar_only) {
-        const int q = C / 4;
-        const int Q = q % 64 == 0 ? 64 : q % 32 == 0 ? 32 : q % 16 == 0 ? 16 : q % 8 == 0 ? 8 : q % 4 == 0 ? 4 : q % 2 == 0 ? 2 : 1;
-        const dim3 grid(C / (4 * Q), P, o.B);
-#define BNACT_Q(QQ) hipLaunchKernelGGL((bnact_q_kernel<TI, TO, TC, QQ>), grid, dim3(256), 0, s, (const TI*)a.in, a.scale, a.shift, has_res ? a.in2 : nullptr, o.res_dtype, \
-                                       has_res ? static_cast<const float*>(a.w2) : nullptr, (TO*)a.out, (TC*)a.out2, a.aux, HW, C, P, o.act)
-        switch (Q) { case 64: BNACT_Q(64); break; case 32: BNACT_Q(32); break; case 16: BNACT_Q(16); break; case 8: BNACT_Q(8); break; case 4: BNACT_Q(4); break;
-                     case 2: BNACT_Q(2); break; default: BNACT_Q(1); }
-#undef BNACT_Q
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL((bnact_kernel<TI, TO, TC>), dim3((C + 63) / 64, P, o.B), dim3(256), 0, s, (const TI*)a.in, a.scale, a.shift, has_res ? a.in2 : nullptr,
-                       o.res_dtype, has_res ? static_cast<const float*>(a.w2) : nullptr, (TO*)a.out, (TC*)a.out2, a.aux, HW, C, P, o.act);
+    const int HW = o.H * o.W, C = o.Cin, P = c.P;
+    const dim3 grid(c.grid[0], c.grid[1], c.grid[2]);
+    const void* res = c.has_res ? a.in2 : nullptr;
+    const float* keep = c.has_res ? static_cast<const float*>(a.w2) : nullptr;
+    if (c.family == train::BN_Q)
+        train::with_quads(c.Q, [&](auto q) {
+            hipLaunchKernelGGL((bnact_q_kernel<TI, TO, TC, decltype(q)::value>), grid, dim3(256), 0, s, (const TI*)a.in, a.scale, a.shift, res, o.res_dtype, keep, (TO*)a.out,
+                               (TC*)a.out2, a.aux, HW, C, P, o.act);
+        });
+    else
+        hipLaunchKernelGGL((bnact_kernel<TI, TO, TC>), grid, dim3(256), 0, s, (const TI*)a.in, a.scale, a.shift, res, o.res_dtype, keep, (TO*)a.out, (TC*)a.out2, a.aux, HW, C, P,
+                           o.act);
     return hipGetLastError();
 }
-template <typename TI, typename TC>
-hipError_t launch_bnact_i(const OpArgs& a, hipStream_t s) {
-    if (a.op->out_dtype == FTC_F32) return launch_bnact_t<TI, float, TC>(a, s);
-    return launch_bnact_t<TI, TC, TC>(a, s);
+template <typename TC>
+hipError_t launch_bnact_tc(const OpArgs& a, const train::BnactChoice& c, hipStream_t s) {
+    if (c.ti == FTC_F32) return c.to == FTC_F32 ? launch_bnact_t<float, float, TC>(a, c, s) : launch_bnact_t<float, TC, TC>(a, c, s);
+    return c.to == FTC_F32 ? launch_bnact_t<TC, float, TC>(a, c, s) : launch_bnact_t<TC, TC, TC>(a, c, s);
 }
 }  // namespace
 
 hipError_t launch_bnact(const OpArgs& a, hipStream_t s) {
-    const ftc_op& o = *a.op;
-    // TC = the plan's 16-bit type (w_dtype: bf16 unless fp16): 16-bit outputs, copies and residuals come in it
-    if (o.w_dtype == FTC_F16) {
-        if (o.in_dtype == FTC_F32) return launch_bnact_i<float, _Float16>(a, s);
-        return launch_bnact_i<_Float16, _Float16>(a, s);
-    }
-    if (o.in_dtype == FTC_F32) return launch_bnact_i<float, __bf16>(a, s);
-    return launch_bnact_i<__bf16, __bf16>(a, s);
+    train::BnactChoice c;
+    if (train::bnact_resolve(*a.op, &c) != nullptr) return hipErrorInvalidValue;      // (plan creation refuses such ops)
+    return c.tc == FTC_F16 ? launch_bnact_tc<_Float16>(a, c, s) : launch_bnact_tc<__bf16>(a, c, s);
 }
 
 hipError_t launch_topk_mask(const float* vals, long n, long k, unsigned char* mask, int32_t* sel_index, int32_t* count, hipStream_t s) {

@@ -68,6 +68,8 @@ def is_f32(v64: torch.Tensor) -> bool:
 
 
 # ---- launch arithmetic ------------------------------------------------------------------------------------------------------------
+# (restated from the launchers as they stood before csrc/train_choice.h -- the C++ quoted below is theirs -- and kept as the independent statement:
+#  tests/test_bn_operands_host.py holds the resolvers the launchers now consume to it)
 
 def pick_q(C: int) -> int:
     """launch_bnstat / launch_bnact_t (train_ops.hip: `const int Q = q % 64 == 0 ? 64 : ...`), pick_quads (bwd_ops.hip)."""

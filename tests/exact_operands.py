@@ -341,6 +341,35 @@ def dwbwd_case(B, H, W, C, stride, seed=0):
     return SimpleNamespace(x=x, w=w, dz=dz, pre=pre, Ho=Ho, Wo=Wo, want_dx=round_out(dx, L.F32), want_dw=round_out(zw, L.F32))
 
 
+# (id, shape, stride) of test_gpu_exact_bwd.test_dwbwd_exact: C = 96, 24, 384 (Q = 8, 2, 32; the weight pass 8, 2, 16) and one width per remaining lane
+# layout -- C = 4, 16, 64, 256: Q = 1, 4, 16, 64 (the weight pass 1, 4, 16 and, capped, 16); tests/test_exact_operands_host.py proves both lists of Q
+DWBWD_CASES = [("12x10x96_s1", (2, 12, 10, 96), 1), ("12x10x96_s2", (2, 12, 10, 96), 2), ("9x9x24_s1", (1, 9, 9, 24), 1), ("8x8x384_s1", (3, 8, 8, 384), 1),
+               ("8x8x384_s2", (3, 8, 8, 384), 2), ("5x5x4_s1", (1, 5, 5, 4), 1), ("5x5x16_s2", (1, 5, 5, 16), 2), ("6x5x64_s1", (2, 6, 5, 64), 1), ("5x5x256_s2", (1, 5, 5, 256), 2)]
+
+
+def dwbwd_layout(B, H, W, C, stride, data=True, weight=True):
+    """launch_dwbwd (bwd_ops.hip) as it stood before csrc/train_choice.h, restated: what each half of an FTC_OP_DWBWD op launches.
+    data (`if (a.out)`): `if (!old_form && Mi < 0x7fffffffL)` with Mi = B H W -> dwbwd_data_q_kernel<Qd>, Qd = pick_quads(C) (the largest of 64, 32, .. 2
+    dividing C / 4, else 1), RLd = 256 / Qd, `want = (2048L * 4 * Qd) / C` clamped to [1, Mi / (4 RLd) + 1], grid (C / (4 Qd), want); otherwise
+    dwbwd_data_kernel on nblocks(B H W (C / 4)) workgroups: ceil(total / 256) clamped to [1, 16384].
+    weight (`if (a.out2)`): nchunk = ftc_chunks256(B Ho Wo) = ceil(M / 256) clamped to [1, 512], Q = min(pick_quads(C), 16),
+    dwbwd_weight_partial_kernel<Q> on grid (C / (4 Q), nchunk), dwbwd_weight_final_kernel on (9 C + 255) / 256 workgroups."""
+    assert C > 0 and C % 4 == 0 and stride in (1, 2)
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    Mi, Mo = B * H * W, B * Ho * Wo
+    q = next((t for t in (64, 32, 16, 8, 4, 2) if (C // 4) % t == 0), 1)
+    d = wt = None
+    if data and Mi < 0x7fffffff:
+        want = max(1, min((2048 * 4 * q) // C, Mi // (4 * (256 // q)) + 1))
+        d = SimpleNamespace(kernel="dwbwd_data_q_kernel", Q=q, want=want, grid=(C // (4 * q), want))
+    elif data:
+        d = SimpleNamespace(kernel="dwbwd_data_kernel", Q=0, want=0, grid=(max(1, min(16384, -(-(Mi * (C // 4)) // 256))), 1))
+    if weight:
+        qw, nchunk = min(q, 16), max(1, min(512, -(-Mo // 256)))
+        wt = SimpleNamespace(kernel="dwbwd_weight_partial_kernel", Q=qw, nchunk=nchunk, grid=(C // (4 * qw), nchunk), final_grid=(9 * C + 255) // 256)
+    return SimpleNamespace(data=d, weight=wt)
+
+
 def topdgrad_colsum_case(co, off, seed=0):
     """d input of a thin 3x3 top convolution (co * 9 terms) and the bias gradient: the column sums of the map gradient (B*H*W terms + a pre-loaded value)."""
     B, H, W, Ci, CoT = 2, 14, 10, 192, 9

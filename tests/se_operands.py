@@ -55,7 +55,7 @@ import bn_operands as N
 import exact_operands as X
 from findtextcenternet_amd import _lib as L
 
-SE_PCH = 32                                                 # bwd_ops.hip
+SE_PCH = 32                                                 # bwd_ops.hip as it stood before csrc/train_choice.h, as all of layout(): tests/test_se_operands_host.py holds the resolver to it
 U = 4                                                       # rows in flight per lane in sebwd_ds_kernel
 GRADS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
 REGIONS = ("ds", "du2", "mean", "dmean", "da1", "h", "dsp")

@@ -713,6 +713,50 @@ def test_backbone_gpu_cases_reach_every_kernel_instantiation(backbone_choice_hos
     assert sorted(got) == sorted(want), (sorted(set(want) - set(got)), sorted(set(got) - set(want)))
 
 
+# ---- the kernel forms of FTC_OP_BNSTAT, BNACT, BNBWD, DWBWD and SEBWD and the labels of the remaining kinds (csrc/train_choice.h) ---------------
+
+@pytest.fixture(scope="module")
+def train_choice_host(tmp_path_factory):
+    """tests/c_abi/train_choice_host.cc (plain C++ over csrc/train_choice.h alone, its own main) built with AddressSanitizer + UBSan; returns a function that
+    runs it on ops (tests/train_choice_host.py) and returns per op (reason, label, instantiation, launch)."""
+    import train_choice_host as H
+    return H.build(tmp_path_factory.mktemp("train_choice"))
+
+
+def test_train_choice_header_is_host_only_and_clean_under_sanitizers(train_choice_host):
+    """csrc/train_choice.h needs no HIP header: the stand-alone program resolves accepted and refused ops of the five kinds -- every refusal the header has --
+    and answers as the library does: accepted exactly where ftc_plan_create accepts, refused for the reason it gives, labelled as ftc_op_kernel_label labels.
+    The launch arithmetic behind the accepted ones is held to its Python restatements in test_bn_operands_host.py, test_se_operands_host.py and
+    test_exact_operands_host.py; verdicts and messages of thousands more ops are tests/golden/op_extents.json.gz's."""
+    import backbone_choice_sweep as S
+    import train_choice_host as H
+    sh = (2, 5, 13, 24)
+    ok = [H.bnstat(sh), H.bnstat(sh[:3] + (9,), L.F16), H.bnact(sh, L.F32, L.F32, L.BF16, 3, L.BF16, True), H.bnact(sh[:3] + (9,), L.F16, L.F16, L.F16, 0),
+          H.bnbwd(sh, L.F32, L.F32), H.bnbwd(sh, L.BF16, L.BF16, "both", True), H.bnbwd(sh, L.F16, L.F32, "out2"), H.dwbwd(sh, 1), H.dwbwd(sh, 2, "data"),
+          H.dwbwd(sh, 2, "weight"), H.sebwd(sh, 6, 3)]
+    bad = [dict(H.bnstat(sh), B=0), dict(H.bnstat(sh), Cin=0), H.bnstat(sh, 5),
+           dict(H.bnact(sh, L.F32, L.F32, L.BF16), aux0=65536), H.bnact(sh, 5, L.F32, L.BF16), H.bnact(sh, L.F16, L.F32, L.BF16), H.bnact(sh, L.F32, L.F32, L.BF16, 1, L.F16),
+           dict(H.bnact(sh, L.F32, L.F32, L.BF16), act=9), H.bnact(sh, L.F32, L.BF16, L.BF16, 1, None, True),
+           H.bnbwd(sh[:3] + (6,), L.F32, L.F32), dict(H.bnbwd(sh, L.F32, L.F32), Cin_total=16), dict(H.bnbwd(sh, L.F32, L.F32), act=9), dict(H.bnbwd(sh, L.F32, L.F32), _refs=("in_", "in2", "scale", "aux")),
+           H.bnbwd(sh, L.F32, L.F32, "both"), H.bnbwd(sh, L.BF16, L.BF16, "out2", True), H.bnbwd(sh, L.BF16, L.F16),
+           dict(H.dwbwd(sh, 1), stride=3), dict(H.dwbwd(sh, 2), Ho=5), dict(H.dwbwd(sh, 1), _refs=("in2",)),
+           H.sebwd(sh, 0), H.sebwd(sh[:3] + (8000,), 6)]
+    got = train_choice_host(ok + bad)
+    reasons = set()
+    for f, (why, lab, _, _) in zip(ok + bad, got):
+        label, err = S.verdict(S.make_op(f))
+        assert lab == label and (why == "" and err is None if f in ok else why != "" and err is not None and err.endswith(why)), (f, why, lab, label, err)
+        reasons.add(why)
+    assert len(reasons) == 1 + len(bad) == 22                    # each refused op for another reason: the 21 the header holds
+    # the kinds that choose nothing: their labels moved with the five; CONV, WGRAD and the backbone kinds are not this header's
+    others = [dict(kind=k, w_dtype=dt, stride=2) for k in (L.OP_NMS, L.OP_TAPSUM, L.OP_GATHER_ROWS, L.OP_LOSSES, L.OP_LOSS_BWD, L.OP_SCATTER_ROWS, L.OP_UPCATBWD, L.OP_DILATE,
+                                                            L.OP_TOPDGRAD, L.OP_COLSUM, L.OP_STEMWGRAD, L.OP_FILL, L.OP_JOIN) for dt in (L.F32, L.BF16, L.F16)]
+    for f, (why, lab, _, _) in zip(others, train_choice_host(others, letter="l")):
+        assert why == "" and lab == S.label(S.make_op(f)), (f, why, lab)
+    theirs = [dict(kind=k) for k in (L.OP_CONV, L.OP_WGRAD, L.OP_STEM, L.OP_DWCONV, L.OP_SE, L.OP_MBHEAD, L.OP_FMBCONV, L.OP_UPCAT, 0, 99)]
+    assert all(why == "no label" and lab == "" for why, lab, _, _ in train_choice_host(theirs, letter="l"))
+
+
 # ---- plan construction and weight packing against the recorded ones (tests/plan_sweep.py) ----------------------------------------
 
 @pytest.fixture(scope="module")

@@ -320,3 +320,117 @@ def test_bnbwd_checks_catch_a_dropped_row_chunk_and_a_missed_reload(cid):
         for b in range(1, c.shape[0]):
             assert _fails("bnbwd", c, {"image": b})
             assert _fails("bnbwd", c, {"image": b}, only=3 if c.outputs != "out2" else 4)
+
+
+# ---- the resolvers of csrc/train_choice.h against the launch arithmetic restated in bn_operands.layout ------------------------------------------------
+
+@pytest.fixture(scope="module")
+def train_choice_host(tmp_path_factory):
+    import train_choice_host as H
+    return H.build(tmp_path_factory.mktemp("train_choice"))
+
+
+def _grid_x(k, C):
+    """layout(): the Q kernels run on grid (C / 4Q, chunks ...), the scalar kernels on ((C + 63) / 64, chunks ...)."""
+    return (C + 63) // 64 if k.path == "scalar" else C // (4 * k.Q)
+
+
+def _bn_agrees(op, shape, lay, got, meta):
+    why, _, inst, launch = got
+    B, H, W, C = shape
+    assert why == "", (meta, why)
+    k = lay[0]
+    assert inst.get("family", "q") == ("scalar" if k.path == "scalar" else "q") and inst["Q"] == (k.Q or 0), (meta, inst)
+    if op == "bnstat":
+        assert (launch["M"], launch["nchunk"], launch["grid"], launch["final"]) == (B * H * W, k.nchunk, (_grid_x(k, C), k.nchunk), (C + 15) // 16), (meta, launch)
+    elif op == "bnact":
+        assert (launch["P"], launch["grid"]) == (k.nchunk, (_grid_x(k, C), k.nchunk, B)), (meta, launch)
+    else:
+        a = lay[1]
+        assert (k.Q, k.RL) == (a.Q, a.RL)
+        assert (launch["M"], launch["nchunk"], launch["ach"]) == (B * H * W, k.nchunk, a.nchunk), (meta, launch)
+        assert (launch["partial"], launch["final"], launch["apply"]) == ((_grid_x(k, C), k.nchunk), (C + 15) // 16, (_grid_x(a, C), a.nchunk)), (meta, launch)
+
+
+def _bn_op(op, kw):
+    import train_choice_host as H
+    if op == "bnstat":
+        return H.bnstat(kw["shape"], kw.get("idt", L.F32))
+    if op == "bnact":
+        return H.bnact(kw["shape"], kw["idt"], kw["odt"], kw["tc"], kw["P"], kw["res"], kw["out2"])
+    return H.bnbwd(kw["shape"], kw["wd"], kw["zdt"], kw["outputs"], kw["variant"] == "slice_accum")
+
+
+@pytest.mark.parametrize("op", ["bnstat", "bnact", "bnbwd"])
+def test_resolver_equals_layout_on_every_gpu_case(op, train_choice_host):
+    """Every case of the three GPU case lists: the family, Q, chunk counts and grids the launcher takes from the resolver are layout()'s, the type arguments
+    are the case's, and the label is the one the op always had."""
+    got = train_choice_host([_bn_op(op, kw) for kw in CASES[op].values()])
+    for (cid, kw), g in zip(CASES[op].items(), got):
+        _bn_agrees(op, kw["shape"], _lay(op, cid), g, cid)
+        inst, launch = g[2], g[3]
+        if op == "bnstat":
+            assert inst["T"] == N.DT_NAME[kw.get("idt", L.F32)] and g[1] == f"bnstat_partial+final<{inst['T']}>", (cid, g)
+        elif op == "bnact":
+            assert (inst["TI"], inst["TO"], inst["TC"]) == tuple(N.DT_NAME[kw[t]] for t in ("idt", "odt", "tc")) and launch["res"] == int(kw["res"] is not None), (cid, g)
+            assert g[1] == f"bnact_kernel<{inst['TI']},{inst['TO']}>", (cid, g)
+        else:
+            assert (inst["fast"], inst["TC"], inst["ZT"]) == (int(kw["wd"] != L.F32), N.DT_NAME[kw["wd"]], N.DT_NAME[kw["zdt"]]), (cid, g)
+            assert launch["accum"] == int(kw["variant"] == "slice_accum") and g[1] == "bnbwd_partial+final+apply", (cid, g)
+    assert {g[2]["Q"] for g in got} >= {64, 32, 16, 8, 4, 2, 1}
+
+
+# B H W of the sweeps.  M = 1 and 7: the apply pass of BNBWD has one chunk (M / 8 + 1 = 1); 130 and 135: 17 chunks, the clamp, at every width but those whose
+# 16384 Q / C is 15 or 16; 8192: M / 8 + 1 = 1025 bounds the wide layouts only.  The BNACT sweep takes H W of each as the rows of one image.
+_BN_SHAPES = [(1, 1, 1), (1, 1, 7), (2, 5, 13), (3, 5, 9), (2, 64, 64)]
+_DTS = (L.F32, L.BF16, L.F16)
+
+
+def test_bnstat_resolver_equals_layout_over_every_width_and_type(train_choice_host):
+    """C = 1 .. 1056 x the shapes x the three input types: the Q kernel exactly for fp32 input with C % 4 == 0, the scalar kernel otherwise."""
+    keys = [(shape + (C,), dt) for C in range(1, 1057) for shape in _BN_SHAPES for dt in _DTS]
+    for (shape, dt), g in zip(keys, train_choice_host([_bn_op("bnstat", dict(shape=shape, idt=dt)) for shape, dt in keys])):
+        _bn_agrees("bnstat", shape, N.layout("bnstat", shape, dt), g, (shape, dt))
+        assert (g[2]["family"] == "q") == (dt == L.F32 and shape[3] % 4 == 0) and g[2]["T"] == N.DT_NAME[dt]
+    # 512 chunks at the most (layout() on the two large shapes of the case list is part of the test above); 2^31 - 1 rows and more: the scalar kernel, whose
+    # row index is 64 bits wide (launch_bnstat: `o.in_dtype == FTC_F32 && C % 4 == 0 && M < 0x7fffffffL`)
+    (_, _, inst, launch), (_, _, inst1, _) = train_choice_host([_bn_op("bnstat", dict(shape=(2, 32768, 32768, 8))), _bn_op("bnstat", dict(shape=(2, 32768, 32767, 8)))])
+    assert (inst["family"], inst["Q"], launch["M"], launch["nchunk"], launch["grid"]) == ("scalar", 0, 2 ** 31, 512, (1, 512)) and (inst1["family"], inst1["Q"]) == ("q", 2)
+    bad = train_choice_host([_bn_op("bnstat", dict(shape=(1, 1, 1, 0))), _bn_op("bnstat", dict(shape=(1, 1, 1, 8), idt=7)), _bn_op("bnstat", dict(shape=(0, 1, 1, 8)))])
+    assert [g[0] for g in bad] == ["bnstat: Cin must be positive", "bnstat: unknown dtype", "B/H/W must be positive"]
+
+
+def test_bnact_resolver_equals_layout_over_every_width_and_type(train_choice_host):
+    """C = 1 .. 1056 x the shapes x P in {0 (= 1), 1, 3, H W + 5} x the plan's three storage forms (fp32 in and out, the 16-bit type in and out, 16-bit in and
+    fp32 out): the Q kernel exactly for C % 4 == 0, whatever the types; FTC_BNACT_SCALAR: the scalar kernel at every width."""
+    forms = [(L.F32, L.F32, L.BF16), (L.BF16, L.BF16, L.BF16), (L.F16, L.F32, L.F16)]
+    keys = [((4,) + shape[1:] + (C,), P, f) for C in range(1, 1057) for shape in _BN_SHAPES[1:4] for P in (0, 1, 3, shape[1] * shape[2] + 5) for f in forms]
+    ops = [_bn_op("bnact", dict(shape=shape, idt=f[0], odt=f[1], tc=f[2], P=P, res=None, out2=False)) for shape, P, f in keys]
+    for (shape, P, f), g in zip(keys, train_choice_host(ops)):
+        _bn_agrees("bnact", shape, N.layout("bnact", shape, f[0], P), g, (shape, P, f))
+        assert (g[2]["family"] == "q") == (shape[3] % 4 == 0) and (g[2]["TI"], g[2]["TO"], g[2]["TC"]) == tuple(N.DT_NAME[t] for t in f)
+    for value, fam in (("1", "scalar"), ("0", "q"), ("", "q")):
+        sw = train_choice_host(ops[:600], env={"FTC_BNACT_SCALAR": value})
+        assert all(g[0] == "" and g[2]["family"] == ("q" if fam == "q" and k[0][3] % 4 == 0 else "scalar") and g[3]["grid"][0] == (k[0][3] // (4 * g[2]["Q"]) if g[2]["Q"] else (k[0][3] + 63) // 64)
+                   for k, g in zip(keys, sw)), value
+
+
+def test_bnbwd_resolver_equals_layout_over_every_width_and_type(train_choice_host):
+    """C = 1 .. 1056 x the shapes x (w_dtype, z type) in (fp32, fp32), (bf16, bf16), (fp16, fp32): widths that are no multiple of 4 are refused with plan
+    creation's message; the apply pass has one chunk, M / 8 + 1 chunks under the clamp, and 16384 Q / C chunks where the clamp does not bind."""
+    forms = [(L.F32, L.F32), (L.BF16, L.BF16), (L.F16, L.F32)]
+    keys = [(shape + (C,), f) for C in range(1, 1057) for shape in _BN_SHAPES for f in forms]
+    got = train_choice_host([_bn_op("bnbwd", dict(shape=shape, wd=f[0], zdt=f[1], outputs="out" if f[0] == L.F32 else "both", variant="plain")) for shape, f in keys])
+    one = clamped = free = 0
+    for (shape, f), g in zip(keys, got):
+        if shape[3] % 4:
+            assert g[0] == "bnbwd: Cin must be a positive multiple of 4", (shape, g)
+            continue
+        lay = N.layout("bnbwd", shape)
+        _bn_agrees("bnbwd", shape, lay, g, (shape, f))
+        assert (g[2]["fast"], g[2]["TC"], g[2]["ZT"]) == (int(f[0] != L.F32), N.DT_NAME[f[0]], N.DT_NAME[f[1]])
+        M, raw, ach = shape[0] * shape[1] * shape[2], (4096 * 4 * lay[1].Q) // shape[3], g[3]["ach"]
+        one += ach == 1
+        clamped += 1 < ach == M // 8 + 1 < raw
+        free += 1 < ach == raw < M // 8 + 1
+    assert one and clamped and free, (one, clamped, free)

@@ -89,7 +89,7 @@ def test_wgrad_cases_are_exact_and_order_free(case):
 
 
 def test_other_backward_cases_are_exact():
-    for shape, stride in [((2, 12, 10, 96), 1), ((2, 12, 10, 96), 2), ((1, 9, 9, 24), 1), ((3, 8, 8, 384), 1), ((3, 8, 8, 384), 2)]:
+    for _, shape, stride in X.DWBWD_CASES:
         c = X.dwbwd_case(*shape, stride, seed=shape[3] + stride)
         xx, ww = c.x.clone().requires_grad_(True), c.w.clone().requires_grad_(True)
         F.conv2d(xx.permute(0, 3, 1, 2), ww, None, stride, 1, 1, shape[3]).backward(c.dz.permute(0, 3, 1, 2))
@@ -179,3 +179,75 @@ def test_mutated_references_differ(name):
         x[0, 0, 0, 0] = x[0, 0, j, 0]
         z = _ref(c, x=x)
     assert int((z != c.z).sum()) >= 1
+
+
+# ---- FTC_OP_DWBWD: the resolver of csrc/train_choice.h against launch_dwbwd restated (exact_operands.dwbwd_layout) -------------------------------------
+
+@pytest.fixture(scope="module")
+def train_choice_host(tmp_path_factory):
+    import train_choice_host as H
+    return H.build(tmp_path_factory.mktemp("train_choice"))
+
+
+def _dwbwd_agrees(shape, stride, halves, got):
+    why, lab, inst, launch = got
+    lay = X.dwbwd_layout(*shape, stride, data=halves != "weight", weight=halves != "data")
+    assert why == "" and lab == f"dwbwd_data+weight<s{stride}>", (shape, stride, halves, why, lab)
+    d, w = lay.data, lay.weight
+    assert inst["data"] == ("-" if d is None else "q" if d.kernel == "dwbwd_data_q_kernel" else "general") and inst["weight"] == ("-" if w is None else "q"), (shape, inst)
+    assert (inst["Q"], launch["want"], launch["grid"]) == ((d.Q, d.want, d.grid) if d else (0, 0, (0, 0))), (shape, stride, halves, inst, launch)
+    assert (inst["wQ"], launch["nchunk"], launch["wgrid"], launch["wfinal"]) == ((w.Q, w.nchunk, w.grid, w.final_grid) if w else (0, 0, (0, 0), 0)), (shape, stride, halves, inst, launch)
+    return lay
+
+
+def test_dwbwd_gpu_cases_reach_every_lane_layout_of_both_passes(train_choice_host):
+    import train_choice_host as H
+    ops = [H.dwbwd(shape, stride) for _, shape, stride in X.DWBWD_CASES]
+    lays = [_dwbwd_agrees(shape, stride, "both", got) for (_, shape, stride), got in zip(X.DWBWD_CASES, train_choice_host(ops))]
+    assert {k.data.Q for k in lays} == {64, 32, 16, 8, 4, 2, 1} and {k.weight.Q for k in lays} == {16, 8, 4, 2, 1}
+    by_id = {cid: k for (cid, _, _), k in zip(X.DWBWD_CASES, lays)}
+    assert [(by_id[i].data.Q, by_id[i].weight.Q) for i in ("5x5x4_s1", "5x5x16_s2", "6x5x64_s1", "5x5x256_s2")] == [(1, 1), (4, 4), (16, 16), (64, 16)]
+    assert all(k.data.kernel == "dwbwd_data_q_kernel" for k in lays)
+
+
+# B H W of the sweep: the row-chunk clamp Mi / (4 RL) + 1 of the data pass is active at every Q on the first (Mi = 25), at the wider Q only on the next two, and
+# inactive at every Q on the last; the weight pass has 1, 1, 12 | 27 and 257 | 65 chunks (stride 1 | 2)
+_DW_SHAPES = [(1, 5, 5), (2, 12, 10), (3, 48, 48), (2, 160, 205)]
+
+
+def test_dwbwd_resolver_equals_the_restated_launcher_over_every_width(train_choice_host):
+    """Every C from 1 to 1056 x the shapes above x stride 1 | 2 x (both halves, data alone, weight alone): widths that are no multiple of 4 are refused with
+    plan creation's message, every other op resolves to the kernel, Q, row chunks and grids launch_dwbwd took."""
+    import train_choice_host as H
+    keys = [(shape + (Cc,), stride, halves) for Cc in range(1, 1057) for shape in _DW_SHAPES for stride in (1, 2) for halves in ("both", "data", "weight")]
+    got = train_choice_host([H.dwbwd(shape, stride, halves) for shape, stride, halves in keys])
+    clamped = free = low = 0
+    for (shape, stride, halves), g in zip(keys, got):
+        if shape[3] % 4:
+            assert g[0] == "dwbwd: Cin % 4 == 0, stride 1 | 2", (shape, g)
+            continue
+        lay = _dwbwd_agrees(shape, stride, halves, g)
+        if lay.data:
+            raw, most = (2048 * 4 * lay.data.Q) // shape[3], shape[0] * shape[1] * shape[2] // (4 * (256 // lay.data.Q)) + 1
+            clamped += lay.data.want == most < raw
+            free += 1 < lay.data.want == raw < most
+            low += lay.data.want == 1
+    assert clamped and free and low, (clamped, free, low)          # the upper clamp active, inactive, and a single chunk
+    none = train_choice_host([dict(H.dwbwd((1, 5, 5, 8), 1), _refs=("in2",)), dict(H.dwbwd((1, 5, 5, 8), 1), stride=3), dict(H.dwbwd((1, 5, 5, 8), 2), Ho=5)])
+    assert [g[0] for g in none] == ["dwbwd: neither out (data gradient) nor out2 (weight gradient)", "dwbwd: Cin % 4 == 0, stride 1 | 2", "dwbwd: Ho/Wo inconsistent"]
+
+
+def test_dwbwd_general_kernel_from_2_31_input_pixels_and_under_the_switch(train_choice_host):
+    """B H W >= 2^31 - 1: the data pass runs dwbwd_data_kernel on 16384 workgroups; one pixel row less: the Q kernel.  FTC_DWBWD_DATA_OLD: the general
+    kernel at any size; "0" and empty leave the default."""
+    import train_choice_host as H
+    big, under = (2, 32768, 32768), (1, 32768, 65535)
+    assert big[0] * big[1] * big[2] == 2 ** 31 and under[0] * under[1] * under[2] < 2 ** 31 - 1
+    keys = [(shape + (Cc,), stride, "both") for shape in (big, under) for Cc in (4, 24, 96, 256, 1056) for stride in (1, 2)] + [(big[:2] + (32768 - 1, 8), 1, "data")]
+    lays = [_dwbwd_agrees(*k, g) for k, g in zip(keys, train_choice_host([H.dwbwd(*k) for k in keys]))]
+    assert all((k.data.kernel, k.data.grid) == ("dwbwd_data_kernel", (16384, 1)) for key, k in zip(keys, lays) if key[0][:3] == big)
+    assert all(k.data.kernel == "dwbwd_data_q_kernel" for key, k in zip(keys, lays) if key[0][:3] != big)
+    small = H.dwbwd((1, 5, 5, 8), 1)
+    for value, want in (("1", "general"), ("yes", "general"), ("0", "q"), ("", "q")):
+        (why, _, inst, launch), = train_choice_host([small], env={"FTC_DWBWD_DATA_OLD": value})
+        assert why == "" and inst["data"] == want and (want == "q" or launch["grid"] == (1, 1)), (value, inst, launch)

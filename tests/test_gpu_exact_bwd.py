@@ -75,10 +75,10 @@ def test_wgrad_exact(case, wd, io):
     assert bool((ar.buf[ar.size:ar.size + 256] == 0xCD).all())
 
 
-@pytest.mark.parametrize("shape,stride", [((2, 12, 10, 96), 1), ((2, 12, 10, 96), 2), ((1, 9, 9, 24), 1), ((3, 8, 8, 384), 1), ((3, 8, 8, 384), 2)],
-                         ids=["12x10x96_s1", "12x10x96_s2", "9x9x24_s1", "8x8x384_s1", "8x8x384_s2"])
+@pytest.mark.parametrize("shape,stride", [c[1:] for c in X.DWBWD_CASES], ids=[c[0] for c in X.DWBWD_CASES])
 def test_dwbwd_exact(shape, stride):
-    """FTC_OP_DWBWD: the data gradient and the weight gradient (accumulated on a pre-loaded one)."""
+    """FTC_OP_DWBWD: the data gradient and the weight gradient (accumulated on a pre-loaded one), at every lane layout Q either pass can take
+    (exact_operands.DWBWD_CASES; tests/test_exact_operands_host.py shows which)."""
     B, H, W, Cc = shape
     c = X.dwbwd_case(B, H, W, Cc, stride, seed=Cc + stride)
     ar = Arena()

@@ -170,3 +170,63 @@ def test_checks_catch_an_fp32_combination_of_the_partial_sums():
     assert float((good.ds - bad.ds).abs().max() / good.ds.abs().max()) < 5e-5
     e = case("q64_c256_hw1024_pch32_two_full_trips")
     assert torch.equal(E.sebwd_model64(e, {"fp32": True}).ds, e.ref.ds)
+
+
+# ---- the resolver of csrc/train_choice.h against launch_sebwd restated in se_operands.layout ------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def train_choice_host(tmp_path_factory):
+    import train_choice_host as H
+    return H.build(tmp_path_factory.mktemp("train_choice"))
+
+
+def _se_agrees(shape, S, k, got, meta):
+    why, lab, inst, launch = got
+    B, H, W, C = shape
+    cb = (C + 255) // 256                                                           # the three (C + 255) / 256 kernels
+    assert why == "" and lab == "sebwd_ds+mlp+w", (meta, why, lab)
+    assert (inst["Q"], launch["pch"], launch["ds"]) == (k.Q, k.pch, (C // (4 * k.Q), k.pch, B)), (meta, inst, launch)
+    assert (launch["prep"], launch["hidden"], launch["dmean"], launch["w"], launch["lds"]) == ((cb, B), ((S + 3) // 4, B), (cb, B), (cb, S), 4 * S), (meta, launch)
+    off = E.offsets(B, C, S, k.pch)
+    assert (launch["bs"], launch["dsp"], launch["scratch"]) == (off["da1"][0], off["dsp"][0], E.scratch_floats(B, C, S)), (meta, launch)
+    assert off["h"][0] == launch["bs"] + B * S and launch["dsp"] + E.SE_PCH * B * C == launch["scratch"]
+
+
+def test_resolver_equals_layout_on_every_gpu_case(train_choice_host):
+    import train_choice_host as H
+    got = train_choice_host([H.sebwd(kw["shape"], kw["S"], kw["P"]) for kw in CASES.values()])
+    for (cid, kw), g in zip(CASES.items(), got):
+        _se_agrees(kw["shape"], kw["S"], _lay(cid), g, cid)
+    assert {g[2]["Q"] for g in got} == {64, 32, 16, 8, 4, 2, 1}
+
+
+# B H W of the sweep: H W = 1024 leaves pch to the first step of its rule (B = 1: SE_PCH up to C = 128 Q; B = 4 with 257 workgroups along C and more: the lower
+# clamp, 1024 / (groups B) = 0); H W = 64, 100 and 729 cut it to 4, 6 and 45 > SE_PCH (no cut); H W = 2: HW / 16 = 0, one chunk
+_SE_SHAPES = [(1, 32, 32), (4, 32, 32), (3, 8, 8), (3, 10, 10), (3, 27, 27), (4, 1, 2), (8, 16, 32)]
+
+
+def test_resolver_equals_layout_over_every_width(train_choice_host):
+    """C = 1 .. 1056 x the shapes x S in {1, 6, 300}: widths that are no multiple of 4 are refused with plan creation's message; Q, pch, the five grids, the
+    dynamic LDS and the scratch offsets are what launch_sebwd computed.  pch is seen at 1 (by the lower clamp, by the rule itself and by the cut), at SE_PCH,
+    between the two uncut, and cut by HW / 16."""
+    import train_choice_host as H
+    keys = [(shape + (C,), S) for C in range(1, 1057) for shape in _SE_SHAPES for S in (1, 6, 300)]
+    got = train_choice_host([H.sebwd(shape, S, 3) for shape, S in keys])
+    seen = dict.fromkeys(("clamped_to_1", "rule_gives_1", "cut_to_1", "at_se_pch", "between_uncut", "cut_between"), 0)
+    for (shape, S), g in zip(keys, got):
+        B, Hh, W, C = shape
+        if C % 4:
+            assert g[0] == "sebwd: C (% 4 == 0), S, P must be positive", (shape, g)
+            continue
+        k = E.layout(*shape)
+        _se_agrees(shape, S, k, g, (shape, S))
+        raw = 1024 // ((C // (4 * k.Q)) * B)
+        seen["clamped_to_1"] += raw == 0 and k.pch == 1
+        seen["rule_gives_1"] += raw == 1 and not k.cut
+        seen["cut_to_1"] += k.cut and k.pch == 1
+        seen["at_se_pch"] += k.pch == E.SE_PCH and raw >= E.SE_PCH
+        seen["between_uncut"] += not k.cut and 1 < k.pch == raw < E.SE_PCH
+        seen["cut_between"] += k.cut and 1 < k.pch == k.HW // 16
+    assert all(seen.values()), seen
+    bad = train_choice_host([H.sebwd((1, 4, 4, 8), 0), H.sebwd((1, 4, 4, 8), 6, 0), H.sebwd((1, 4, 4, 7996), 4), H.sebwd((1, 4, 4, 7996), 5), H.sebwd((1, 0, 4, 8), 6)])
+    assert [g[0] for g in bad] == ["sebwd: C (% 4 == 0), S, P must be positive"] * 2 + ["", "sebwd: C / S too large for LDS", "B/H/W must be positive"]          # (2 C + 2 S) * 4 <= 64000
