@@ -56,6 +56,10 @@ TEXT_BWD_EXPORTS = ["ftc_text_bwd_abi_version", "ftc_text_attention_bwd_workspac
                     "ftc_text_rownorm_bwd", "ftc_text_swiglu_bwd", "ftc_text_loss_workspace_bytes", "ftc_text_loss"]
 TEXT_ROWS_EXPORTS = ["ftc_text_rows_abi_version", "ftc_text_rownorm_rows", "ftc_text_pad_input", "ftc_text_plan_ops"]
 
+# include/ftc_optim.h (the recognizer's optimizer: the Schedule-Free RAdam step and the train() / eval() swap over an MtChunk table)
+FTC_OPTIM_ABI_VERSION = 1
+OPTIM_EXPORTS = ["ftc_optim_abi_version", "ftc_radam_schedulefree_step", "ftc_schedulefree_lerp"]
+
 
 # include/ftc_ocr.h (page-level OCR glue): again its own version and list
 FTC_OCR_ABI_VERSION = 1
@@ -266,6 +270,9 @@ def load():
     lib.ftc_text_loss_workspace_bytes.argtypes = [i64]
     lib.ftc_text_loss_workspace_bytes.restype = i64
     lib.ftc_text_loss.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.ftc_optim_abi_version.restype = i32
+    lib.ftc_radam_schedulefree_step.argtypes = [vp, i32, i32] + [C.c_float] * 8 + [i32, vp]
+    lib.ftc_schedulefree_lerp.argtypes = [vp, i32, C.c_float, vp]
     lib.ftc_ocr_abi_version.restype = i32
     lib.ftc_ocr_assemble.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp, vp]
     lib.ftc_prep_abi_version.restype = i32
@@ -290,6 +297,8 @@ def load():
         raise FtcLibraryError(f"prep ABI mismatch: library {lib.ftc_prep_abi_version()} vs binding {FTC_PREP_ABI_VERSION}")
     if lib.ftc_ocr_abi_version() != FTC_OCR_ABI_VERSION:
         raise FtcLibraryError(f"OCR ABI mismatch: library {lib.ftc_ocr_abi_version()} vs binding {FTC_OCR_ABI_VERSION}")
+    if lib.ftc_optim_abi_version() != FTC_OPTIM_ABI_VERSION:
+        raise FtcLibraryError(f"optimizer ABI mismatch: library {lib.ftc_optim_abi_version()} vs binding {FTC_OPTIM_ABI_VERSION}")
     if lib.ftc_text_bwd_abi_version() != FTC_TEXT_BWD_ABI_VERSION:
         raise FtcLibraryError(f"text backward ABI mismatch: library {lib.ftc_text_bwd_abi_version()} vs binding {FTC_TEXT_BWD_ABI_VERSION}")
     if lib.ftc_text_rows_abi_version() != FTC_TEXT_ROWS_ABI_VERSION:

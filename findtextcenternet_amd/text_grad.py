@@ -19,7 +19,7 @@ CUDA fp32 only; there is no CPU fallback.  Not here: the linear layers' own back
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import torch
 import torch.nn.functional as F
@@ -289,6 +289,10 @@ class TextGrad:
         with torch.no_grad():
             for n, p in self.model.named_parameters():
                 p.copy_(self.params[n].detach().to(p.device))
+
+    def parameters(self) -> List[torch.Tensor]:
+        """The device parameters in ``model.parameters()`` order: what an optimizer is constructed on (``train3.py:120-121``)."""
+        return [self.params[n] for n, _ in self.model.named_parameters()]
 
     def grads(self) -> Dict[str, Optional[torch.Tensor]]:
         return {n: p.grad for n, p in self.params.items()}
