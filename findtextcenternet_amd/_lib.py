@@ -54,6 +54,10 @@ FTC_TEXT_ROWS_ABI_VERSION = 1
 FTC_TEXT_BWD_ABI_VERSION = 1
 TEXT_BWD_EXPORTS = ["ftc_text_bwd_abi_version", "ftc_text_attention_bwd_workspace_bytes", "ftc_text_attention_bwd", "ftc_text_rownorm_bwd_workspace_bytes",
                     "ftc_text_rownorm_bwd", "ftc_text_swiglu_bwd", "ftc_text_loss_workspace_bytes", "ftc_text_loss"]
+# include/ftc_text_linear.h (the recognizer's linear layers: forward, data gradient, weight and bias gradients on the weight as nn.Linear stores it)
+FTC_TEXT_LINEAR_ABI_VERSION = 1
+TEXT_LINEAR_MAX_CHUNKS = 16
+TEXT_LINEAR_EXPORTS = ["ftc_text_linear_abi_version", "ftc_text_linear", "ftc_text_linear_bwd_workspace_bytes", "ftc_text_linear_bwd"]
 TEXT_ROWS_EXPORTS = ["ftc_text_rows_abi_version", "ftc_text_rownorm_rows", "ftc_text_pad_input", "ftc_text_plan_ops"]
 
 # include/ftc_optim.h (the recognizer's optimizer: the Schedule-Free RAdam step and the train() / eval() swap over an MtChunk table)
@@ -270,6 +274,11 @@ def load():
     lib.ftc_text_loss_workspace_bytes.argtypes = [i64]
     lib.ftc_text_loss_workspace_bytes.restype = i64
     lib.ftc_text_loss.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.ftc_text_linear_abi_version.restype = i32
+    lib.ftc_text_linear.argtypes = [vp, i64, vp, i64, vp, vp, i64, i64, i32, i32, vp]
+    lib.ftc_text_linear_bwd_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.ftc_text_linear_bwd_workspace_bytes.restype = i64
+    lib.ftc_text_linear_bwd.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp]
     lib.ftc_optim_abi_version.restype = i32
     lib.ftc_radam_schedulefree_step.argtypes = [vp, i32, i32] + [C.c_float] * 8 + [i32, vp]
     lib.ftc_schedulefree_lerp.argtypes = [vp, i32, C.c_float, vp]
@@ -299,6 +308,8 @@ def load():
         raise FtcLibraryError(f"OCR ABI mismatch: library {lib.ftc_ocr_abi_version()} vs binding {FTC_OCR_ABI_VERSION}")
     if lib.ftc_optim_abi_version() != FTC_OPTIM_ABI_VERSION:
         raise FtcLibraryError(f"optimizer ABI mismatch: library {lib.ftc_optim_abi_version()} vs binding {FTC_OPTIM_ABI_VERSION}")
+    if lib.ftc_text_linear_abi_version() != FTC_TEXT_LINEAR_ABI_VERSION:
+        raise FtcLibraryError(f"text linear ABI mismatch: library {lib.ftc_text_linear_abi_version()} vs binding {FTC_TEXT_LINEAR_ABI_VERSION}")
     if lib.ftc_text_bwd_abi_version() != FTC_TEXT_BWD_ABI_VERSION:
         raise FtcLibraryError(f"text backward ABI mismatch: library {lib.ftc_text_bwd_abi_version()} vs binding {FTC_TEXT_BWD_ABI_VERSION}")
     if lib.ftc_text_rows_abi_version() != FTC_TEXT_ROWS_ABI_VERSION:

@@ -1,20 +1,25 @@
 """Gradients of the text recognizer on the GPU (reference ``models/transformer.py:248-253`` and the loss of ``train3.py:130-134``).
 
 ``torch.autograd.Function`` wrappers over the recognizer's own kernels -- forward through ``include/ftc_text.h``, backward through
-``include/ftc_text_bwd.h`` -- for everything that is not a linear layer:
+``include/ftc_text_bwd.h`` -- for everything that is not a linear layer, and over ``include/ftc_text_linear.h`` for the linear layers:
 
 * ``attention(q, k, v, key_pad)``       fused attention, heads 64 wide, at most 400 positions
 * ``rownorm(...)``                      sums of activations, position tables and token tables, with or without LayerNorm, in the forms the
                                         recognizer's plan uses (``FORMS`` of tests/text_operands.py)
 * ``swiglu(x)``                         ``x[:, :H] * silu(x[:, H:])``
 * ``loss_function3(outputs, labelcode, mask)``   the reference's dict ``{'loss', 'correct', 'total'}``, ``loss`` differentiable
+* ``linear(x, w, bias=None)``           ``x w^T + bias`` on the weight as ``nn.Linear`` stores it: exact-fp32 MFMA, one ascending chain per
+                                        element of the output and of the input's gradient, the weight and bias gradients summed over fixed
+                                        row chunks (``include/ftc_text_linear.h``)
 
-and ``TextGrad(model)``: a device copy of a ``Transformer``'s parameters under the reference's names and one training-mode
-forward + backward through those functions, with ``torch.nn.functional.linear`` for the linear layers (embed, the attention
-projections, the three SwiGLU matrices with the ``+ _x`` that follows the last one, the three output heads).  The sums are in a fixed
-order: a call repeated on the same inputs leaves the same bits in every ``.grad`` that only these kernels produce.
+and ``TextGrad(model, linear="torch" | "hip")``: a device copy of a ``Transformer``'s parameters under the reference's names and one
+training-mode forward + backward through those functions.  The linear layers (embed, the attention projections, the three SwiGLU matrices,
+the three output heads) go through ``torch.nn.functional.linear`` by default and through ``linear`` above with ``linear="hip"``; the
+``torch.cat`` of ``[w1 | wg]`` and the ``+ _x`` that follows ``w2`` are torch ops either way.  The kernels' sums are in a fixed order: a call
+repeated on the same inputs leaves the same bits in every ``.grad`` that only these kernels produce -- with ``linear="hip"`` that is every
+``.grad``, and a batch row's logits do not depend on the rows it is batched with.
 
-CUDA fp32 only; there is no CPU fallback.  Not here: the linear layers' own backward kernels, the optimizer, dropout, 16-bit autocast.
+CUDA fp32 only; there is no CPU fallback.  Not here: dropout, 16-bit autocast (the optimizer is ``findtextcenternet_amd.optim``).
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from .schema import modulo_list
 
-__all__ = ["attention", "rownorm", "swiglu", "loss_function3", "TextGrad"]
+__all__ = ["attention", "rownorm", "swiglu", "loss_function3", "linear", "TextGrad"]
 
 MASK_TOKEN = L.TEXT_MASK_TOKEN          # decoder_MSK
 _NO_CPU = "findtextcenternet_amd.text_grad runs on the GPU only, in fp32 (there is no CPU fallback)"
@@ -205,6 +210,58 @@ def swiglu(x: torch.Tensor) -> torch.Tensor:
     return _SwiGLU.apply(x)
 
 
+class _Linear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        _f32(x, w, bias)
+        if w.dim() != 2 or x.dim() < 1 or x.shape[-1] != w.shape[1] or (bias is not None and bias.shape != (w.shape[0],)):
+            raise ValueError("linear: x [..., K], w [N, K], bias [N] or None")
+        x, w = x.contiguous(), w.contiguous()
+        b = bias.contiguous() if bias is not None else None
+        N, K = w.shape
+        rows = x.numel() // K
+        out = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
+        if rows:
+            with torch.cuda.device(x.device):
+                L.check(L.load().ftc_text_linear(x.data_ptr(), K, w.data_ptr(), K, _ptr(b), out.data_ptr(), N, rows, K, N, _stream(x.device)), "ftc_text_linear")
+        ctx.save_for_backward(x, w)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        lib = L.load()
+        N, K = w.shape
+        rows = x.numel() // K
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x) if need[0] else None
+        dw = torch.empty_like(w) if need[1] else None
+        db = torch.empty(N, dtype=torch.float32, device=w.device) if ctx.has_bias and need[2] else None
+        if dx is None and dw is None and db is None:
+            return None, None, None
+        if rows == 0:
+            for t in (dw, db):
+                if t is not None:
+                    t.zero_()
+            return dx, dw, db
+        dy = dy.contiguous()
+        with torch.cuda.device(x.device):
+            ws = _ws(lib.ftc_text_linear_bwd_workspace_bytes(rows, K, N) if dw is not None or db is not None else 0, x.device)
+            L.check(lib.ftc_text_linear_bwd(x.data_ptr(), K, w.data_ptr(), K, dy.data_ptr(), N, _ptr(dx), K, _ptr(dw), K, _ptr(db), rows, K, N, ws.data_ptr(),
+                                            _stream(x.device)), "ftc_text_linear_bwd")
+        return dx, dw, db
+
+
+def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [..., K] (made contiguous), w [N, K] as ``nn.Linear`` stores it, bias [N] or None -> x w^T + bias [..., N], with gradients
+    (``include/ftc_text_linear.h``: the arithmetic and the order of every sum are the header's)."""
+    return _Linear.apply(x, w, bias)
+
+
+_hip_linear = linear          # TextGrad's constructor has an argument of the same name
+
+
 def _loss_launch(logits, labelcode, mask, want_grad: bool):
     """(loss [1] fp32, counts [2] int64, (d0, d1, d2) or None) of ``ftc_text_loss`` on contiguous [n, m] logits."""
     lib = L.load()
@@ -260,10 +317,15 @@ class TextGrad:
     The model keeps its parameters on the host and runs a packed copy; ``TextGrad`` holds its own fp32 device copy of every parameter
     under the reference's names (``params``), refreshed by ``load_from_module()`` and written back by ``store_to_module()``.
     ``forward_backward`` leaves ``.grad`` on each of them (overwritten, not accumulated).  A self-attention never reads its
-    ``pos_emb_k`` table (``models/transformer.py:104-106``): its ``.grad`` stays ``None``."""
+    ``pos_emb_k`` table (``models/transformer.py:104-106``): its ``.grad`` stays ``None``.  ``linear``: what runs the linear layers,
+    ``"torch"`` (``torch.nn.functional.linear``, the default) or ``"hip"`` (this module's ``linear``)."""
 
-    def __init__(self, model, device=None):
+    def __init__(self, model, device=None, linear="torch"):
         from .transformer import Transformer
+        if linear not in ("torch", "hip"):
+            raise ValueError(f"TextGrad: linear must be 'torch' or 'hip', not {linear!r}")
+        self.linear = linear
+        self._lin = _hip_linear if linear == "hip" else F.linear
         if not isinstance(model, Transformer):
             raise TypeError("TextGrad expects a findtextcenternet_amd Transformer")
         if model.dims.dropout > 0:
@@ -305,16 +367,16 @@ class TextGrad:
 
     def _attn(self, p, xq, xk, xv, key_pad):
         P = self.params
-        q = F.linear(xq, P[p + ".q_proj.weight"])
-        k = F.linear(xk, P[p + ".k_proj.weight"])
-        v = F.linear(xv, P[p + ".v_proj.weight"])
-        return F.linear(attention(q, k, v, key_pad), P[p + ".out_proj.weight"])
+        q = self._lin(xq, P[p + ".q_proj.weight"])
+        k = self._lin(xk, P[p + ".k_proj.weight"])
+        v = self._lin(xv, P[p + ".v_proj.weight"])
+        return self._lin(attention(q, k, v, key_pad), P[p + ".out_proj.weight"])
 
     def _ff(self, p, x):
         P = self.params
         w = torch.cat([P[p + ".w1.weight"], P[p + ".wg.weight"]], 0)
         bias = torch.cat([P[p + ".w1.bias"], P[p + ".wg.bias"]], 0)
-        return F.linear(swiglu(F.linear(x, w, bias)), P[p + ".w2.weight"], P[p + ".w2.bias"]) + x          # x + _x
+        return self._lin(swiglu(self._lin(x, w, bias)), P[p + ".w2.weight"], P[p + ".w2.bias"]) + x          # x + _x
 
     def _ln(self, p):
         return self.params[p + ".weight"], self.params[p + ".bias"]
@@ -339,7 +401,7 @@ class TextGrad:
             return P[prefix + ".pos_emb_q.encoding"]
 
         first_q = pos_q("encoder.blocks.0.mha")[:Ls] if nb_e else None
-        x, xq = rownorm(a=F.linear(x_in, P["encoder.embed.weight"]), pos_in=P["encoder.pos_emb.encoding"][:Ls], gamma=self._ln("encoder.norm")[0],
+        x, xq = rownorm(a=self._lin(x_in, P["encoder.embed.weight"]), pos_in=P["encoder.pos_emb.encoding"][:Ls], gamma=self._ln("encoder.norm")[0],
                         beta=self._ln("encoder.norm")[1], pos_out=first_q)
         for i in range(nb_e):
             p = f"encoder.blocks.{i}"
@@ -364,7 +426,7 @@ class TextGrad:
             g3, b3 = self._ln(p + ".norm3")
             nxt = pos_q(f"decoder.blocks.{i + 1}.self_attn")[:T] if i + 1 < nb_d else None
             y, yq = rownorm(a=self._ff(p + ".ff", y2), b=skip, gamma=g3, beta=b3, pos_out=nxt)
-        return [F.linear(y, P[f"decoder.out_layers.{j}.weight"], P[f"decoder.out_layers.{j}.bias"]) for j in range(3)]
+        return [self._lin(y, P[f"decoder.out_layers.{j}.weight"], P[f"decoder.out_layers.{j}.bias"]) for j in range(3)]
 
     def forward_backward(self, enc_input: torch.Tensor, dec_input: torch.Tensor, label_code: torch.Tensor, grad_scale: float = 1.0):
         """One training step's forward and backward: the loss dict of ``loss_function3(model(enc_input, dec_input), label_code,
