@@ -8,18 +8,27 @@
                                         recognizer's plan uses (``FORMS`` of tests/text_operands.py)
 * ``swiglu(x)``                         ``x[:, :H] * silu(x[:, H:])``
 * ``loss_function3(outputs, labelcode, mask)``   the reference's dict ``{'loss', 'correct', 'total'}``, ``loss`` differentiable
-* ``linear(x, w, bias=None)``           ``x w^T + bias`` on the weight as ``nn.Linear`` stores it: exact-fp32 MFMA, one ascending chain per
-                                        element of the output and of the input's gradient, the weight and bias gradients summed over fixed
-                                        row chunks (``include/ftc_text_linear.h``)
+* ``linear(x, w, bias=None, operands="fp32")``   ``x w^T + bias`` on the weight as ``nn.Linear`` stores it: exact-fp32 MFMA, one ascending
+                                        chain per element of the output and of the input's gradient, the weight and bias gradients summed over
+                                        fixed row chunks (``include/ftc_text_linear.h``); with ``operands="fp16"`` x, w and dy are rounded to
+                                        fp16 (nearest even) as the kernel stages them and the products are summed in fp32 by the f16 MFMA
+                                        (``include/ftc_text_linear_f16.h``) -- tensors, bias and results stay fp32 in memory
 
-and ``TextGrad(model, linear="torch" | "hip")``: a device copy of a ``Transformer``'s parameters under the reference's names and one
+and ``TextGrad(model, linear="torch" | "hip" | "hip_fp16")``: a device copy of a ``Transformer``'s parameters under the reference's names and one
 training-mode forward + backward through those functions.  The linear layers (embed, the attention projections, the three SwiGLU matrices,
-the three output heads) go through ``torch.nn.functional.linear`` by default and through ``linear`` above with ``linear="hip"``; the
+the three output heads) go through ``torch.nn.functional.linear`` by default, through ``linear`` above with ``linear="hip"`` and through ``linear(..., operands="fp16")`` with
+``linear="hip_fp16"``; the
 ``torch.cat`` of ``[w1 | wg]`` and the ``+ _x`` that follows ``w2`` are torch ops either way.  The kernels' sums are in a fixed order: a call
-repeated on the same inputs leaves the same bits in every ``.grad`` that only these kernels produce -- with ``linear="hip"`` that is every
-``.grad``, and a batch row's logits do not depend on the rows it is batched with.
+repeated on the same inputs leaves the same bits in every ``.grad`` that only these kernels produce -- with ``linear="hip"`` or
+``"hip_fp16"`` that is every ``.grad``, and a batch row's logits do not depend on the rows it is batched with.
 
-CUDA fp32 only; there is no CPU fallback.  Not here: dropout, 16-bit autocast (the optimizer is ``findtextcenternet_amd.optim``).
+``linear="hip_fp16"`` is the project's own mixed-precision contract, not a bit replica of ``torch.autocast(float16)``: only the operands of the
+linear layers' products are rounded to fp16; attention, the row kernels (sums, LayerNorm), SwiGLU and the loss stay fp32, as do all activations,
+parameters and gradients in memory.  It is meant to run as the reference's AMP step does (``train3.py:129-134, 151, 180-186``): with a
+``grad_scale`` (65536 is ``GradScaler``'s start) so that small gradients stay above fp16's 2^-24, and an optimizer that skips a step whose
+gradients are not finite -- a gradient of 65520 or more becomes inf in a linear layer's backward.
+
+CUDA fp32 tensors only; there is no CPU fallback.  Not here: dropout, fp16 storage (the optimizer is ``findtextcenternet_amd.optim``).
 """
 from __future__ import annotations
 
@@ -212,8 +221,10 @@ def swiglu(x: torch.Tensor) -> torch.Tensor:
 
 class _Linear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, bias):
+    def forward(ctx, x, w, bias, half):
         _f32(x, w, bias)
+        lib = L.load()
+        fwd = lib.ftc_text_linear_f16 if half else lib.ftc_text_linear
         if w.dim() != 2 or x.dim() < 1 or x.shape[-1] != w.shape[1] or (bias is not None and bias.shape != (w.shape[0],)):
             raise ValueError("linear: x [..., K], w [N, K], bias [N] or None")
         x, w = x.contiguous(), w.contiguous()
@@ -223,15 +234,18 @@ class _Linear(torch.autograd.Function):
         out = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
         if rows:
             with torch.cuda.device(x.device):
-                L.check(L.load().ftc_text_linear(x.data_ptr(), K, w.data_ptr(), K, _ptr(b), out.data_ptr(), N, rows, K, N, _stream(x.device)), "ftc_text_linear")
+                L.check(fwd(x.data_ptr(), K, w.data_ptr(), K, _ptr(b), out.data_ptr(), N, rows, K, N, _stream(x.device)), "ftc_text_linear")
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
+        ctx.half = half
         return out
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
         lib = L.load()
+        bwd, ws_bytes = (lib.ftc_text_linear_f16_bwd, lib.ftc_text_linear_f16_bwd_workspace_bytes) if ctx.half else (
+            lib.ftc_text_linear_bwd, lib.ftc_text_linear_bwd_workspace_bytes)
         N, K = w.shape
         rows = x.numel() // K
         need = ctx.needs_input_grad
@@ -239,27 +253,38 @@ class _Linear(torch.autograd.Function):
         dw = torch.empty_like(w) if need[1] else None
         db = torch.empty(N, dtype=torch.float32, device=w.device) if ctx.has_bias and need[2] else None
         if dx is None and dw is None and db is None:
-            return None, None, None
+            return None, None, None, None
         if rows == 0:
             for t in (dw, db):
                 if t is not None:
                     t.zero_()
-            return dx, dw, db
+            return dx, dw, db, None
         dy = dy.contiguous()
         with torch.cuda.device(x.device):
-            ws = _ws(lib.ftc_text_linear_bwd_workspace_bytes(rows, K, N) if dw is not None or db is not None else 0, x.device)
-            L.check(lib.ftc_text_linear_bwd(x.data_ptr(), K, w.data_ptr(), K, dy.data_ptr(), N, _ptr(dx), K, _ptr(dw), K, _ptr(db), rows, K, N, ws.data_ptr(),
-                                            _stream(x.device)), "ftc_text_linear_bwd")
-        return dx, dw, db
+            ws = _ws(ws_bytes(rows, K, N) if dw is not None or db is not None else 0, x.device)
+            L.check(bwd(x.data_ptr(), K, w.data_ptr(), K, dy.data_ptr(), N, _ptr(dx), K, _ptr(dw), K, _ptr(db), rows, K, N, ws.data_ptr(), _stream(x.device)),
+                    "ftc_text_linear_bwd")
+        return dx, dw, db, None
 
 
-def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x [..., K] (made contiguous), w [N, K] as ``nn.Linear`` stores it, bias [N] or None -> x w^T + bias [..., N], with gradients
-    (``include/ftc_text_linear.h``: the arithmetic and the order of every sum are the header's)."""
-    return _Linear.apply(x, w, bias)
+def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, operands: str = "fp32") -> torch.Tensor:
+    """x [..., K] (made contiguous), w [N, K] as ``nn.Linear`` stores it, bias [N] or None -> x w^T + bias [..., N], with gradients.
+    ``operands="fp32"``: ``include/ftc_text_linear.h``; ``operands="fp16"``: ``include/ftc_text_linear_f16.h`` (x, w and dy rounded to fp16 as they
+    are staged, fp32 sums, fp32 results).  The arithmetic and the order of every sum are the header's."""
+    if operands not in ("fp32", "fp16"):
+        raise ValueError(f"linear: operands must be 'fp32' or 'fp16', not {operands!r}")
+    return _Linear.apply(x, w, bias, operands == "fp16")
 
 
-_hip_linear = linear          # TextGrad's constructor has an argument of the same name
+def _hip_linear(x, w, bias=None):          # TextGrad's constructor has an argument named `linear`
+    return linear(x, w, bias)
+
+
+def _hip_linear_f16(x, w, bias=None):
+    return linear(x, w, bias, "fp16")
+
+
+_LINEARS = {"torch": F.linear, "hip": _hip_linear, "hip_fp16": _hip_linear_f16}
 
 
 def _loss_launch(logits, labelcode, mask, want_grad: bool):
@@ -318,14 +343,15 @@ class TextGrad:
     under the reference's names (``params``), refreshed by ``load_from_module()`` and written back by ``store_to_module()``.
     ``forward_backward`` leaves ``.grad`` on each of them (overwritten, not accumulated).  A self-attention never reads its
     ``pos_emb_k`` table (``models/transformer.py:104-106``): its ``.grad`` stays ``None``.  ``linear``: what runs the linear layers,
-    ``"torch"`` (``torch.nn.functional.linear``, the default) or ``"hip"`` (this module's ``linear``)."""
+    ``"torch"`` (``torch.nn.functional.linear``, the default), ``"hip"`` (this module's ``linear``) or ``"hip_fp16"`` (the same with
+    ``operands="fp16"``: see the module's docstring for what stays fp32)."""
 
     def __init__(self, model, device=None, linear="torch"):
         from .transformer import Transformer
-        if linear not in ("torch", "hip"):
-            raise ValueError(f"TextGrad: linear must be 'torch' or 'hip', not {linear!r}")
+        if linear not in _LINEARS:
+            raise ValueError(f"TextGrad: linear must be 'torch', 'hip' or 'hip_fp16', not {linear!r}")
         self.linear = linear
-        self._lin = _hip_linear if linear == "hip" else F.linear
+        self._lin = _LINEARS[linear]
         if not isinstance(model, Transformer):
             raise TypeError("TextGrad expects a findtextcenternet_amd Transformer")
         if model.dims.dropout > 0:
