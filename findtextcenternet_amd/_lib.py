@@ -90,6 +90,15 @@ DISTORT_MAX_RADIUS = 32
 SAMPLE_AUG_EXPORTS = ["ftc_sample_aug_abi_version", "ftc_sample_synth_salt", "ftc_sample_distort_workspace_bytes", "ftc_sample_distort",
                       "ftc_sample_normal_fill"]
 
+# include/ftc_text_sample.h (the recognizer's training batch: gen_feature / pad_output of the reference's data_transformer.py on the device)
+FTC_TEXT_SAMPLE_ABI_VERSION = 1
+TEXT_SAMPLE_FEATURE_DIM, TEXT_SAMPLE_FLAG_COLS, TEXT_SAMPLE_ROWS, TEXT_SAMPLE_CODES = 100, 6, 400, 400
+TEXT_SAMPLE_PAD, TEXT_SAMPLE_SOT, TEXT_SAMPLE_EOT, TEXT_SAMPLE_MSK = 0, 1, 2, 3
+TEXT_SAMPLE_MAX_CHARS = 2048
+TEXT_SAMPLE_HORIZONTAL = 1
+TEXT_BANK_VALID = 0x46544231
+TEXT_SAMPLE_EXPORTS = ["ftc_text_sample_abi_version", "ftc_text_bank_init", "ftc_text_sample"]
+
 
 class FtcLibraryError(RuntimeError):
     pass
@@ -162,6 +171,22 @@ class DistortDesc(C.Structure):
     """ftc_distort_desc of include/ftc_sample_aug.h: 304 bytes, no padding."""
     _fields_ = [("noise", C.c_void_p), ("seed", C.c_uint64), ("alpha", C.c_double), ("w", C.c_double * (DISTORT_MAX_RADIUS + 1)),
                 ("flags", C.c_int32), ("radius", C.c_int32), ("k", C.c_float), ("reserved", C.c_int32)]
+
+
+class TextBankEntry(C.Structure):
+    """ftc_text_bank_entry of include/ftc_text_sample.h: 20 bytes."""
+    _fields_ = [(n, C.c_int32) for n in ("code", "hori_offset", "hori_count", "vert_offset", "vert_count")]
+
+
+class TextBank(C.Structure):
+    """ftc_text_bank of include/ftc_text_sample.h: 32 bytes."""
+    _fields_ = [("rows", C.c_void_p), ("table", C.c_void_p), ("n_rows", C.c_int32), ("n_codes", C.c_int32), ("valid", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class TextSampleDesc(C.Structure):
+    """ftc_text_sample_desc of include/ftc_text_sample.h: 96 bytes, no padding."""
+    _fields_ = [(n, C.c_void_p) for n in ("pick", "n", "z", "u")] + [(n, C.c_uint64) for n in ("seed_pick", "seed_n", "seed_z", "seed_u")] + [
+        ("noise_ratio", C.c_double), ("p", C.c_double), ("text_offset", C.c_int64), ("n_chars", C.c_int32), ("flags", C.c_int32)]
 
 
 _lib = None
@@ -306,6 +331,11 @@ def load():
     lib.ftc_sample_distort_workspace_bytes.restype = i64
     lib.ftc_sample_distort.argtypes = [C.POINTER(DistortDesc), vp, i32, i32, i32, vp, vp, i64, vp]
     lib.ftc_sample_normal_fill.argtypes = [C.c_uint64, i64, vp, vp]
+    lib.ftc_text_sample_abi_version.restype = i32
+    lib.ftc_text_bank_init.argtypes = [C.POINTER(TextBank), vp, C.POINTER(TextBankEntry), vp, i32, i32]
+    lib.ftc_text_sample.argtypes = [C.POINTER(TextBank), C.POINTER(TextSampleDesc), vp, i32, vp, i64, vp, i32, vp, vp, vp]
+    if lib.ftc_text_sample_abi_version() != FTC_TEXT_SAMPLE_ABI_VERSION:
+        raise FtcLibraryError(f"text sample ABI mismatch: library {lib.ftc_text_sample_abi_version()} vs binding {FTC_TEXT_SAMPLE_ABI_VERSION}")
     if lib.ftc_sample_aug_abi_version() != FTC_SAMPLE_AUG_ABI_VERSION:
         raise FtcLibraryError(f"sample-aug ABI mismatch: library {lib.ftc_sample_aug_abi_version()} vs binding {FTC_SAMPLE_AUG_ABI_VERSION}")
     if lib.ftc_sample_abi_version() != FTC_SAMPLE_ABI_VERSION:
