@@ -61,6 +61,10 @@ TEXT_LINEAR_EXPORTS = ["ftc_text_linear_abi_version", "ftc_text_linear", "ftc_te
 # include/ftc_text_linear_f16.h (the same calls on operands rounded to fp16 as they are staged: v_mfma_f32_32x32x16_f16, fp32 sums)
 FTC_TEXT_LINEAR_F16_ABI_VERSION = 1
 TEXT_LINEAR_F16_EXPORTS = ["ftc_text_linear_f16_abi_version", "ftc_text_linear_f16", "ftc_text_linear_f16_bwd_workspace_bytes", "ftc_text_linear_f16_bwd"]
+# include/ftc_text_attention_f16.h (fused attention, forward and backward, on operands rounded to fp16: the training path, no kv_row form)
+FTC_TEXT_ATTENTION_F16_ABI_VERSION = 1
+TEXT_ATTENTION_F16_EXPORTS = ["ftc_text_attention_f16_abi_version", "ftc_text_attention_f16", "ftc_text_attention_f16_bwd_workspace_bytes",
+                              "ftc_text_attention_f16_bwd"]
 TEXT_ROWS_EXPORTS = ["ftc_text_rows_abi_version", "ftc_text_rownorm_rows", "ftc_text_pad_input", "ftc_text_plan_ops"]
 
 # include/ftc_optim.h (the recognizer's optimizer: the Schedule-Free RAdam step and the train() / eval() swap over an MtChunk table)
@@ -312,6 +316,11 @@ def load():
     lib.ftc_text_linear_f16_bwd_workspace_bytes.argtypes = [i64, i32, i32]
     lib.ftc_text_linear_f16_bwd_workspace_bytes.restype = i64
     lib.ftc_text_linear_f16_bwd.argtypes = lib.ftc_text_linear_bwd.argtypes
+    lib.ftc_text_attention_f16_abi_version.restype = i32
+    lib.ftc_text_attention_f16.argtypes = lib.ftc_text_attention.argtypes
+    lib.ftc_text_attention_f16_bwd_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.ftc_text_attention_f16_bwd_workspace_bytes.restype = i64
+    lib.ftc_text_attention_f16_bwd.argtypes = lib.ftc_text_attention_bwd.argtypes
     lib.ftc_optim_abi_version.restype = i32
     lib.ftc_radam_schedulefree_step.argtypes = [vp, i32, i32] + [C.c_float] * 8 + [i32, vp]
     lib.ftc_schedulefree_lerp.argtypes = [vp, i32, C.c_float, vp]
@@ -346,6 +355,8 @@ def load():
         raise FtcLibraryError(f"OCR ABI mismatch: library {lib.ftc_ocr_abi_version()} vs binding {FTC_OCR_ABI_VERSION}")
     if lib.ftc_optim_abi_version() != FTC_OPTIM_ABI_VERSION:
         raise FtcLibraryError(f"optimizer ABI mismatch: library {lib.ftc_optim_abi_version()} vs binding {FTC_OPTIM_ABI_VERSION}")
+    if lib.ftc_text_attention_f16_abi_version() != FTC_TEXT_ATTENTION_F16_ABI_VERSION:
+        raise FtcLibraryError(f"text attention fp16 ABI mismatch: library {lib.ftc_text_attention_f16_abi_version()} vs binding {FTC_TEXT_ATTENTION_F16_ABI_VERSION}")
     if lib.ftc_text_linear_f16_abi_version() != FTC_TEXT_LINEAR_F16_ABI_VERSION:
         raise FtcLibraryError(f"text linear fp16 ABI mismatch: library {lib.ftc_text_linear_f16_abi_version()} vs binding {FTC_TEXT_LINEAR_F16_ABI_VERSION}")
     if lib.ftc_text_linear_abi_version() != FTC_TEXT_LINEAR_ABI_VERSION:

@@ -3,7 +3,9 @@
 ``torch.autograd.Function`` wrappers over the recognizer's own kernels -- forward through ``include/ftc_text.h``, backward through
 ``include/ftc_text_bwd.h`` -- for everything that is not a linear layer, and over ``include/ftc_text_linear.h`` for the linear layers:
 
-* ``attention(q, k, v, key_pad)``       fused attention, heads 64 wide, at most 400 positions
+* ``attention(q, k, v, key_pad, operands="fp32")``   fused attention, heads 64 wide, at most 400 positions; with ``operands="fp16"`` q, k, v, P, dO
+                                        and dS are rounded to fp16 (nearest even) as they become MFMA operands and the products are summed in
+                                        fp32 by the f16 MFMA (``include/ftc_text_attention_f16.h``) -- tensors and results stay fp32 in memory
 * ``rownorm(...)``                      sums of activations, position tables and token tables, with or without LayerNorm, in the forms the
                                         recognizer's plan uses (``FORMS`` of tests/text_operands.py)
 * ``swiglu(x)``                         ``x[:, :H] * silu(x[:, H:])``
@@ -14,7 +16,7 @@
                                         fp16 (nearest even) as the kernel stages them and the products are summed in fp32 by the f16 MFMA
                                         (``include/ftc_text_linear_f16.h``) -- tensors, bias and results stay fp32 in memory
 
-and ``TextGrad(model, linear="torch" | "hip" | "hip_fp16")``: a device copy of a ``Transformer``'s parameters under the reference's names and one
+and ``TextGrad(model, linear="torch" | "hip" | "hip_fp16", attention="hip" | "hip_fp16")``: a device copy of a ``Transformer``'s parameters under the reference's names and one
 training-mode forward + backward through those functions.  The linear layers (embed, the attention projections, the three SwiGLU matrices,
 the three output heads) go through ``torch.nn.functional.linear`` by default, through ``linear`` above with ``linear="hip"`` and through ``linear(..., operands="fp16")`` with
 ``linear="hip_fp16"``; the
@@ -22,11 +24,15 @@ the three output heads) go through ``torch.nn.functional.linear`` by default, th
 repeated on the same inputs leaves the same bits in every ``.grad`` that only these kernels produce -- with ``linear="hip"`` or
 ``"hip_fp16"`` that is every ``.grad``, and a batch row's logits do not depend on the rows it is batched with.
 
-``linear="hip_fp16"`` is the project's own mixed-precision contract, not a bit replica of ``torch.autocast(float16)``: only the operands of the
-linear layers' products are rounded to fp16; attention, the row kernels (sums, LayerNorm), SwiGLU and the loss stay fp32, as do all activations,
-parameters and gradients in memory.  It is meant to run as the reference's AMP step does (``train3.py:129-134, 151, 180-186``): with a
-``grad_scale`` (65536 is ``GradScaler``'s start) so that small gradients stay above fp16's 2^-24, and an optimizer that skips a step whose
-gradients are not finite -- a gradient of 65520 or more becomes inf in a linear layer's backward.
+``linear="hip_fp16"`` and ``attention="hip_fp16"`` are the project's own mixed-precision contract, not a bit replica of
+``torch.autocast(float16)``: only the operands of the linear layers' products and -- with ``attention="hip_fp16"``, in all three attention sites
+(encoder self, decoder self, decoder cross) -- of the attention's products (q, k, v, the softmax weights P, dO and dS) are rounded to fp16; the
+softmax itself, the row kernels (sums, LayerNorm), SwiGLU and the loss stay fp32, as do all activations, parameters and gradients in memory.
+With ``attention="hip"`` (the default) attention stays fp32 throughout.  The modes are meant to run as the reference's AMP step does
+(``train3.py:129-134, 151, 180-186``): with a ``grad_scale`` (65536 is ``GradScaler``'s start) so that small gradients stay above fp16's 2^-24, and
+an optimizer that skips a step whose gradients are not finite -- a gradient of 65520 or more becomes inf in a linear layer's backward, and with
+``attention="hip_fp16"`` so does a scaled dS (the gradient of a score) of 65520 or more: the gradients of that step are not finite and
+``GradScaler`` skips it.
 
 CUDA fp32 tensors only; there is no CPU fallback.  Not here: dropout, fp16 storage (the optimizer is ``findtextcenternet_amd.optim``).
 """
@@ -69,8 +75,9 @@ def _ws(nbytes: int, dev) -> torch.Tensor:
 
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, key_pad):
+    def forward(ctx, q, k, v, key_pad, half):
         _f32(q, k, v)
+        fwd = L.load().ftc_text_attention_f16 if half else L.load().ftc_text_attention
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         B, Sq, E = q.shape
         Sk = k.shape[1]
@@ -83,29 +90,36 @@ class _Attention(torch.autograd.Function):
                 raise ValueError("attention: key_pad must be [B, Sk] on the GPU")
         out = torch.empty_like(q)
         with torch.cuda.device(q.device):
-            L.check(L.load().ftc_text_attention(q.data_ptr(), E, k.data_ptr(), E, v.data_ptr(), E, _ptr(pad), out.data_ptr(), E, B, E // 64, Sq, Sk,
-                                                _stream(q.device)), "ftc_text_attention")
+            L.check(fwd(q.data_ptr(), E, k.data_ptr(), E, v.data_ptr(), E, _ptr(pad), out.data_ptr(), E, B, E // 64, Sq, Sk, _stream(q.device)),
+                    "ftc_text_attention")
         ctx.save_for_backward(q, k, v, pad)
+        ctx.half = half
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, pad = ctx.saved_tensors
         lib = L.load()
+        bwd, ws_bytes = (lib.ftc_text_attention_f16_bwd, lib.ftc_text_attention_f16_bwd_workspace_bytes) if ctx.half else (
+            lib.ftc_text_attention_bwd, lib.ftc_text_attention_bwd_workspace_bytes)
         B, Sq, E = q.shape
         Sk = k.shape[1]
         dout = dout.contiguous()
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         with torch.cuda.device(q.device):
-            ws = _ws(lib.ftc_text_attention_bwd_workspace_bytes(B, E // 64, Sq, Sk), q.device)
-            L.check(lib.ftc_text_attention_bwd(q.data_ptr(), E, k.data_ptr(), E, v.data_ptr(), E, _ptr(pad), dout.data_ptr(), E, dq.data_ptr(), E, dk.data_ptr(), E,
-                                               dv.data_ptr(), E, B, E // 64, Sq, Sk, ws.data_ptr(), _stream(q.device)), "ftc_text_attention_bwd")
-        return dq, dk, dv, None
+            ws = _ws(ws_bytes(B, E // 64, Sq, Sk), q.device)
+            L.check(bwd(q.data_ptr(), E, k.data_ptr(), E, v.data_ptr(), E, _ptr(pad), dout.data_ptr(), E, dq.data_ptr(), E, dk.data_ptr(), E, dv.data_ptr(), E,
+                        B, E // 64, Sq, Sk, ws.data_ptr(), _stream(q.device)), "ftc_text_attention_bwd")
+        return dq, dk, dv, None, None
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """softmax(q k^T / 8 + mask) v per head of 64 columns: q [B, Sq, E], k / v [B, Sk, E], key_pad [B, Sk] (non-zero: never attended to) or None."""
-    return _Attention.apply(q, k, v, key_pad)
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, key_pad: Optional[torch.Tensor] = None, operands: str = "fp32") -> torch.Tensor:
+    """softmax(q k^T / 8 + mask) v per head of 64 columns: q [B, Sq, E], k / v [B, Sk, E], key_pad [B, Sk] (non-zero: never attended to) or None.
+    ``operands="fp32"``: ``ftc_text_attention`` / ``ftc_text_attention_bwd``; ``operands="fp16"``: ``include/ftc_text_attention_f16.h`` (q, k, v, P,
+    dO and dS rounded to fp16 as they become MFMA operands, fp32 sums and softmax, fp32 results).  The arithmetic is the header's."""
+    if operands not in ("fp32", "fp16"):
+        raise ValueError(f"attention: operands must be 'fp32' or 'fp16', not {operands!r}")
+    return _Attention.apply(q, k, v, key_pad, operands == "fp16")
 
 
 class _RowNorm(torch.autograd.Function):
@@ -285,6 +299,7 @@ def _hip_linear_f16(x, w, bias=None):
 
 
 _LINEARS = {"torch": F.linear, "hip": _hip_linear, "hip_fp16": _hip_linear_f16}
+_ATTENTIONS = {"hip": "fp32", "hip_fp16": "fp16"}          # TextGrad's attention= -> attention()'s operands=
 
 
 def _loss_launch(logits, labelcode, mask, want_grad: bool):
@@ -344,14 +359,21 @@ class TextGrad:
     ``forward_backward`` leaves ``.grad`` on each of them (overwritten, not accumulated).  A self-attention never reads its
     ``pos_emb_k`` table (``models/transformer.py:104-106``): its ``.grad`` stays ``None``.  ``linear``: what runs the linear layers,
     ``"torch"`` (``torch.nn.functional.linear``, the default), ``"hip"`` (this module's ``linear``) or ``"hip_fp16"`` (the same with
-    ``operands="fp16"``: see the module's docstring for what stays fp32)."""
+    ``operands="fp16"``: see the module's docstring for what stays fp32).  ``attention``: ``"hip"`` (fp32 fused attention, the default) or
+    ``"hip_fp16"`` (``attention(..., operands="fp16")`` in the encoder's self-attention and the decoder's self- and cross-attention).
+    With ``linear="hip_fp16"`` it is the faster step (40.1 ms against 49.2 ms at B = 8 on the default recognizer) and the one that
+    has the shape of the reference's AMP step; run it with a ``grad_scale``."""
 
-    def __init__(self, model, device=None, linear="torch"):
+    def __init__(self, model, device=None, linear="torch", attention="hip"):
         from .transformer import Transformer
         if linear not in _LINEARS:
             raise ValueError(f"TextGrad: linear must be 'torch', 'hip' or 'hip_fp16', not {linear!r}")
+        if attention not in _ATTENTIONS:
+            raise ValueError(f"TextGrad: attention must be 'hip' or 'hip_fp16', not {attention!r}")
         self.linear = linear
         self._lin = _LINEARS[linear]
+        self.attention = attention
+        self._attn_operands = _ATTENTIONS[attention]
         if not isinstance(model, Transformer):
             raise TypeError("TextGrad expects a findtextcenternet_amd Transformer")
         if model.dims.dropout > 0:
@@ -396,7 +418,7 @@ class TextGrad:
         q = self._lin(xq, P[p + ".q_proj.weight"])
         k = self._lin(xk, P[p + ".k_proj.weight"])
         v = self._lin(xv, P[p + ".v_proj.weight"])
-        return self._lin(attention(q, k, v, key_pad), P[p + ".out_proj.weight"])
+        return self._lin(attention(q, k, v, key_pad, self._attn_operands), P[p + ".out_proj.weight"])
 
     def _ff(self, p, x):
         P = self.params
