@@ -2,7 +2,8 @@
 the one rounding to float16), the codes and the mask, and the integer parts of the seeded draws (the Philox-derived pick and mask
 uniforms).  tests/golden/g24_text_sample.npz (written by tests/golden/gen_golden_text_sample.py from the reference's own
 TransformerDataDataset with a scripted rng) pins this file against the reference; tests/test_gpu_text_sample.py holds the device to the
-same rules.
+same rules.  tests/text_sample_long.py adds the long structured texts (and tests/golden/g26_text_sample_long.npz the reference's arrays
+on them) that make every stage of the kernel's scans decide a flag.
 
 `faults` switches on one deliberate deviation at a time (tests/test_text_sample_host.py: every one of them must show in the fixture)."""
 import hashlib
