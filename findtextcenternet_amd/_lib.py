@@ -65,6 +65,9 @@ TEXT_LINEAR_F16_EXPORTS = ["ftc_text_linear_f16_abi_version", "ftc_text_linear_f
 FTC_TEXT_ATTENTION_F16_ABI_VERSION = 1
 TEXT_ATTENTION_F16_EXPORTS = ["ftc_text_attention_f16_abi_version", "ftc_text_attention_f16", "ftc_text_attention_f16_bwd_workspace_bytes",
                               "ftc_text_attention_f16_bwd"]
+# include/ftc_text_attention16.h (inference attention on fp16 / bf16 operands with the kv_row form, and the per-handle switch that selects it)
+FTC_TEXT_ATTENTION16_ABI_VERSION = 1
+TEXT_ATTENTION16_EXPORTS = ["ftc_text_attention16_abi_version", "ftc_text_attention16", "ftc_text_set_attention", "ftc_text_get_attention"]
 TEXT_ROWS_EXPORTS = ["ftc_text_rows_abi_version", "ftc_text_rownorm_rows", "ftc_text_pad_input", "ftc_text_plan_ops"]
 
 # include/ftc_optim.h (the recognizer's optimizer: the Schedule-Free RAdam step and the train() / eval() swap over an MtChunk table)
@@ -321,6 +324,10 @@ def load():
     lib.ftc_text_attention_f16_bwd_workspace_bytes.argtypes = [i32, i32, i32, i32]
     lib.ftc_text_attention_f16_bwd_workspace_bytes.restype = i64
     lib.ftc_text_attention_f16_bwd.argtypes = lib.ftc_text_attention_bwd.argtypes
+    lib.ftc_text_attention16_abi_version.restype = i32
+    lib.ftc_text_attention16.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i32, vp, i64, i32, i32, i32, i32, i32, vp]
+    lib.ftc_text_set_attention.argtypes = [vp, i32]
+    lib.ftc_text_get_attention.argtypes = [vp]
     lib.ftc_optim_abi_version.restype = i32
     lib.ftc_radam_schedulefree_step.argtypes = [vp, i32, i32] + [C.c_float] * 8 + [i32, vp]
     lib.ftc_schedulefree_lerp.argtypes = [vp, i32, C.c_float, vp]
@@ -355,6 +362,8 @@ def load():
         raise FtcLibraryError(f"OCR ABI mismatch: library {lib.ftc_ocr_abi_version()} vs binding {FTC_OCR_ABI_VERSION}")
     if lib.ftc_optim_abi_version() != FTC_OPTIM_ABI_VERSION:
         raise FtcLibraryError(f"optimizer ABI mismatch: library {lib.ftc_optim_abi_version()} vs binding {FTC_OPTIM_ABI_VERSION}")
+    if lib.ftc_text_attention16_abi_version() != FTC_TEXT_ATTENTION16_ABI_VERSION:
+        raise FtcLibraryError(f"text attention16 ABI mismatch: library {lib.ftc_text_attention16_abi_version()} vs binding {FTC_TEXT_ATTENTION16_ABI_VERSION}")
     if lib.ftc_text_attention_f16_abi_version() != FTC_TEXT_ATTENTION_F16_ABI_VERSION:
         raise FtcLibraryError(f"text attention fp16 ABI mismatch: library {lib.ftc_text_attention_f16_abi_version()} vs binding {FTC_TEXT_ATTENTION_F16_ABI_VERSION}")
     if lib.ftc_text_linear_f16_abi_version() != FTC_TEXT_LINEAR_F16_ABI_VERSION:

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libftc_hip.so")
 SOURCES = ["conv_igemm_bf16_fb.hip", "conv_igemm_bf16_ff.hip", "conv_igemm_f16_fh.hip", "conv_igemm_f16_ff.hip",
-           "conv_igemm_f32.hip", "conv_igemm_x3.hip", "conv_igemm.hip", "conv1x1_px144.hip", "backbone_ops.hip", "mbconv_slice.hip", "mbconv_slice_x3.hip", "fused_mbconv.hip", "conv3x3_c32.hip", "fpn_ops.hip", "decode.hip", "glyph_select.hip", "maskpredict_select.hip", "text_attention.hip", "text_ops.hip", "ftc_text.hip", "text_attention_bwd.hip", "text_ops_bwd.hip", "text_loss.hip", "text_linear.hip", "text_linear_f16.hip", "text_attention_f16.hip", "ocr_assemble.hip", "page_ops.hip", "page_merge.hip", "page_fill.hip", "sample_synth.hip", "sample_distort.hip", "text_sample.hip", "optim.hip", "optim_radam.hip", "train_ops.hip", "bwd_ops.hip", "wgrad.hip", "ftc_api.hip", "pack.hip", "plan.hip", "model.hip"]
+           "conv_igemm_f32.hip", "conv_igemm_x3.hip", "conv_igemm.hip", "conv1x1_px144.hip", "backbone_ops.hip", "mbconv_slice.hip", "mbconv_slice_x3.hip", "fused_mbconv.hip", "conv3x3_c32.hip", "fpn_ops.hip", "decode.hip", "glyph_select.hip", "maskpredict_select.hip", "text_attention.hip", "text_ops.hip", "ftc_text.hip", "text_attention_bwd.hip", "text_ops_bwd.hip", "text_loss.hip", "text_linear.hip", "text_linear_f16.hip", "text_attention_f16.hip", "text_attention_16.hip", "ocr_assemble.hip", "page_ops.hip", "page_merge.hip", "page_fill.hip", "sample_synth.hip", "sample_distort.hip", "text_sample.hip", "optim.hip", "optim_radam.hip", "train_ops.hip", "bwd_ops.hip", "wgrad.hip", "ftc_api.hip", "pack.hip", "plan.hip", "model.hip"]
 HEADERS = [os.path.join(CSRC, "ftc_common.h"), os.path.join(CSRC, "conv_igemm_impl.h"), os.path.join(CSRC, "conv_choice.h"), os.path.join(CSRC, "wgrad_choice.h"), os.path.join(CSRC, "backbone_choice.h"), os.path.join(CSRC, "train_choice.h"), os.path.join(CSRC, "op_extents.h"), os.path.join(os.path.dirname(HERE), "include", "ftc.h"),
            os.path.join(CSRC, "ftc_host.h"), os.path.join(CSRC, "crt_wave.h"), os.path.join(CSRC, "text_math.h"), os.path.join(os.path.dirname(HERE), "include", "ftc_text.h")]
 EXTRA_DEPS = {"ocr_assemble.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_ocr.h")],
@@ -31,6 +31,9 @@ EXTRA_DEPS.update({"text_linear_f16.hip": [os.path.join(os.path.dirname(HERE), "
                                            os.path.join(os.path.dirname(HERE), "include", "ftc_text_linear.h"),
                                            os.path.join(CSRC, "text_linear_choice.h")]})      # the same layers on fp16 operands: the same choice header
 EXTRA_DEPS.update({"text_attention_f16.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_text_attention_f16.h")]})      # attention on fp16 operands
+TEXT_ATTENTION16_H = os.path.join(os.path.dirname(HERE), "include", "ftc_text_attention16.h")      # inference attention on fp16 / bf16 operands, and the handle's switch
+EXTRA_DEPS.update({"text_attention_16.hip": [TEXT_ATTENTION16_H]})
+EXTRA_DEPS["ftc_text.hip"].append(TEXT_ATTENTION16_H)
 PHILOX_H = os.path.join(CSRC, "philox_normal.h")       # Philox4x32-10 / Box-Muller: the sample distortion's noise, the recognizer batch's draws
 EXTRA_DEPS["sample_distort.hip"].append(PHILOX_H)
 EXTRA_DEPS.update({"text_sample.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_text_sample.h"), PHILOX_H]})      # the recognizer's training batch

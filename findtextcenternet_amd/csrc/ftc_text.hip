@@ -39,11 +39,15 @@
 #include "../../include/ftc_text.h"
 #include "../../include/ftc_text_compact.h"
 #include "../../include/ftc_text_rows.h"
+#include "../../include/ftc_text_attention16.h"
 
 hipError_t ftc_text_attention_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad,
                                      float* out, int64_t ldo, int B, int heads, int Sq, int Sk, hipStream_t stream);
 hipError_t ftc_text_attention_rows_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad,
                                           const int32_t* kv_row, int Bkv, float* out, int64_t ldo, int B, int heads, int Sq, int Sk, hipStream_t stream);
+hipError_t ftc_text_attention16_launch(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, const uint8_t* key_pad,
+                                       const int32_t* kv_row, int Bkv, float* out, int64_t ldo, int B, int heads, int Sq, int Sk, int operands,
+                                       hipStream_t stream);
 hipError_t ftc_text_rownorm_rows_launch(const float* a, const float* b, const float* pos_in, const float* gamma, const float* beta, const float* pos_out,
                                         const int64_t* tokens, const float* e0, const float* e1, const float* e2, const int32_t* tok_row, int tok_rows,
                                         float* out, float* out_pos, int64_t rows, int S, int E, hipStream_t stream);
@@ -115,6 +119,7 @@ struct TextPlan {
 struct ftc_text {
     ftc_text_dims d;
     int precision = FTC_F32;                 // FTC_F32 | FTC_BF16 | FTC_F16 | FTC_PRECISION_F16X3
+    int attention = FTC_F32;                 // the attention's operands: FTC_F32 | FTC_F16 | FTC_BF16 (include/ftc_text_attention16.h)
     std::vector<uint8_t> blob;
     std::map<std::string, int64_t> off;
     std::mutex mu;
@@ -327,6 +332,13 @@ struct PlanBuilder {
         const int B_ = B, n_ = n, heads = h->d.head_num, E = h->d.embed_dim;
         const int64_t pad = masked ? P->L.pad : -1;
         const int64_t map = cross && compact() ? map_off() : -1;
+        if (const int operands = h->attention; operands != FTC_F32)          // the same launch on 16-bit operands (ftc_text_set_attention)
+            return [=](const Ctx& c) {
+                auto f = [&](int64_t o) { return reinterpret_cast<float*>(c.ws + o); };
+                return hip(ftc_text_attention16_launch(f(q), ldq, f(k), ldk, f(v), ldv, pad < 0 ? nullptr : reinterpret_cast<const uint8_t*>(c.ws + pad),
+                                                       map < 0 ? nullptr : reinterpret_cast<const int32_t*>(c.ws + map), map < 0 ? n_ : B_, f(out), E, n_, heads,
+                                                       S, S, operands, c.s), "attention");
+            };
         return [=](const Ctx& c) {
             auto f = [&](int64_t o) { return reinterpret_cast<float*>(c.ws + o); };
             return hip(ftc_text_attention_rows_launch(f(q), ldq, f(k), ldk, f(v), ldv, pad < 0 ? nullptr : reinterpret_cast<const uint8_t*>(c.ws + pad),
@@ -619,6 +631,21 @@ int ftc_text_predict_compact(ftc_text* h, const void* weights_dev, const float* 
     }
     if (passes_run) *passes_run = pass;
     return rc;
+}
+
+int ftc_text_set_attention(ftc_text* h, int operands) {
+    if (!h) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_set_attention: null handle");
+    if (operands != FTC_F32 && operands != FTC_F16 && operands != FTC_BF16)
+        return ftc_set_error(FTC_ERR_INVALID, "ftc_text_set_attention: operands must be FTC_F32, FTC_F16 or FTC_BF16");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->attention = operands;
+    h->plans.clear();                        // a call in flight keeps its plan alive (shared_ptr); the next one builds with the new choice
+    return FTC_OK;
+}
+
+int ftc_text_get_attention(const ftc_text* h) {
+    if (!h) { ftc_set_error(FTC_ERR_INVALID, "ftc_text_get_attention: null handle"); return -1; }
+    return h->attention;
 }
 
 static bool ld_ok(int64_t ld, int heads) { return ld >= 64 * (int64_t)heads && ld % 4 == 0; }

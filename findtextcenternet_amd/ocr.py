@@ -470,11 +470,12 @@ def run_pages(pages: Sequence, detect: Callable, linedetect: Callable, recognize
 class OCR_hip_Processer:
     """The fourth backend next to the reference's ``OCR_{torch,onnx,coreml}_Processer``, complete in itself: ``call_OCR(target_file)`` reads
     an image and writes ``target_file + '.json'``; ``ocr_page(im_u8)`` is the same without file I/O; ``ocr_pages`` / ``call_OCR_files`` do many pages at once.  ``linedetect`` is the reference's line
-    finder (``textline_detect``), a separate program the user builds from the reference; it runs as a child process on the CPU."""
+    finder (``textline_detect``), a separate program the user builds from the reference; it runs as a child process on the CPU.
+    ``text_attention`` is the ``attention=`` of the ``Transformer`` built here (None: the fp32 attention; 'match' follows ``text_precision``)."""
 
     def __init__(self, model_size: str = "xl", precision: Optional[str] = None, text_precision: Optional[str] = None,
                  linedetect: str = "textline_detect/linedetect", linedetect_timeout: float = 600, step_ratio: float = 0.6, cut_off: float = 0.4,
-                 detector=None, transformer=None):
+                 detector=None, transformer=None, text_attention: Optional[str] = None):
         from .decode import HipDetectorBackend
         from .detector import CenterNetDetector, TextDetectorModel
         from .schema import ModelDimensions
@@ -491,10 +492,10 @@ class OCR_hip_Processer:
             if os.path.exists("model3.pt"):
                 data = torch.load("model3.pt", map_location="cpu", weights_only=True)
                 config = ModelDimensions(**data["config"])
-                model3 = Transformer(**config.__dict__, precision=text_precision)
+                model3 = Transformer(**config.__dict__, precision=text_precision, attention=text_attention)
                 model3.load_state_dict(data["model_state_dict"])
             else:
-                model3 = Transformer(**ModelDimensions().__dict__, precision=text_precision)
+                model3 = Transformer(**ModelDimensions().__dict__, precision=text_precision, attention=text_attention)
             transformer = TransformerPredictor(model3.encoder, model3.decoder)
         transformer.to(self.device)
         transformer.eval()

@@ -39,6 +39,20 @@ from .schema import ModelDimensions, max_decoderlen, modulo_list, transformer_sc
 
 __all__ = ["ModelDimensions", "Transformer", "TransformerPredictor", "HipTextBackend", "recognize_chunks"]
 
+ATTENTION_OPERANDS = {"fp32": L.F32, "fp16": L.F16, "bf16": L.BF16}          # include/ftc_text_attention16.h
+_MATCH = {"fp32": "fp32", "fp16x3": "fp32", "fp16": "fp16", "bf16": "bf16"}          # attention="match": the operands that go with a precision
+
+
+def resolve_attention(attention: Optional[str], precision: str) -> str:
+    """The ``attention=`` keyword of ``Transformer`` as one of 'fp32', 'fp16', 'bf16'."""
+    attention = attention or "fp32"
+    if attention == "match":
+        return _MATCH[precision]
+    if attention not in ATTENTION_OPERANDS:
+        raise ValueError("attention must be None, 'fp32', 'fp16', 'bf16' or 'match'")
+    return attention
+
+
 _NO_CPU = "findtextcenternet_amd: the text recognizer runs on MI355X (gfx950) only (there is no CPU fallback)"
 
 
@@ -50,9 +64,9 @@ class _TextEngine:
     """The packed model (``ftc_text_create``), its device blob and one workspace per device; shared by a ``Transformer`` and the
     predictors built from its encoder / decoder."""
 
-    def __init__(self, owner: "Transformer", dims: ModelDimensions, precision: str):
+    def __init__(self, owner: "Transformer", dims: ModelDimensions, precision: str, attention: str = "fp32"):
         self._owner = weakref.ref(owner)          # no cycle: the engine (and its native handle) goes when the Transformer does
-        self.dims, self.precision = dims, precision
+        self.dims, self.precision, self.attention = dims, precision, attention
         self.handle: Optional[int] = None
         self.fingerprint = None
         self.wdev: Optional[torch.Tensor] = None
@@ -100,6 +114,8 @@ class _TextEngine:
         h = C.c_void_p()
         L.check(lib.ftc_text_create(arr, len(sd), C.byref(cd), PRECISIONS[self.precision], C.byref(h)), "ftc_text_create")
         self.handle, self.fingerprint = h.value, fp
+        if self.attention != "fp32":          # a new handle launches the fp32 attention: nothing is called for the default
+            L.check(lib.ftc_text_set_attention(self.handle, ATTENTION_OPERANDS[self.attention]), "ftc_text_set_attention")
 
     def ensure(self, dev: torch.device) -> None:
         self.create()
@@ -151,14 +167,18 @@ def _refuse_empty_rows(nonzero_rows) -> None:
 
 class Transformer(nn.Module):
     """models/transformer.py:229-245, eval mode.  ``forward(enc_input, dec_input)`` is one teacher-forced pass and returns the three
-    logit tensors ``[B, 400, 1091 | 1093 | 1097]``.  ``precision``: 'fp32' (default), 'fp16x3', 'fp16', 'bf16' -- the GEMM arithmetic."""
+    logit tensors ``[B, 400, 1091 | 1093 | 1097]``.  ``precision``: 'fp32' (default), 'fp16x3', 'fp16', 'bf16' -- the GEMM arithmetic.
+    ``attention``: the operands of the fused attention (``include/ftc_text_attention16.h``) -- None / 'fp32' (default: the fp32 kernel), 'fp16',
+    'bf16', or 'match' (bf16 -> 'bf16', fp16 -> 'fp16', fp32 and fp16x3 -> 'fp32'); ``model.attention`` holds the resolved name.  Everything built
+    from the model (``TransformerPredictor``, ``HipTextBackend``, ``recognize_chunks``, ``recognize_layout(s)``, the compact loop) runs with it."""
 
     def __init__(self, enc_input_dim, embed_dim, head_num, enc_block_num=6, dec_block_num=6, max_enc_seq_len=5000, max_dec_seq_len=5000,
-                 dropout=0.1, precision: Optional[str] = None):
+                 dropout=0.1, precision: Optional[str] = None, attention: Optional[str] = None):
         super().__init__()
         precision = precision or "fp32"
         if precision not in PRECISIONS:
             raise ValueError("precision must be 'fp32', 'fp16x3', 'bf16' or 'fp16'")
+        attention = resolve_attention(attention, precision)
         if embed_dim % head_num != 0:
             raise ValueError(f"embed_dim ({embed_dim}) must be a multiple of head_num ({head_num})")
         if embed_dim // head_num != 64 or head_num > 16:
@@ -171,6 +191,7 @@ class Transformer(nn.Module):
         self.head_num = head_num
         self.max_len = max(max_enc_seq_len, max_dec_seq_len)
         self.precision = precision
+        self.attention = attention
         from .weights import sinusoid_table
         for name, (shape, kind) in transformer_schema(self.dims).items():
             if kind == "posenc":
@@ -188,7 +209,7 @@ class Transformer(nn.Module):
         for sub in (self.encoder, self.decoder):
             sub.head_num = head_num
         self.decoder.max_seq_len = max_dec_seq_len
-        eng = _TextEngine(self, self.dims, precision)
+        eng = _TextEngine(self, self.dims, precision, attention)
         object.__setattr__(self, "_engine", eng)
         for sub in (self.encoder, self.decoder):
             object.__setattr__(sub, "_engine", eng)
