@@ -73,6 +73,10 @@ TEXT_ROWS_EXPORTS = ["ftc_text_rows_abi_version", "ftc_text_rownorm_rows", "ftc_
 # include/ftc_optim.h (the recognizer's optimizer: the Schedule-Free RAdam step and the train() / eval() swap over an MtChunk table)
 FTC_OPTIM_ABI_VERSION = 1
 OPTIM_EXPORTS = ["ftc_optim_abi_version", "ftc_radam_schedulefree_step", "ftc_schedulefree_lerp"]
+# include/ftc_optim_amp.h (the same optimizer's schedule on the device and its fused AMP step: non-finite scan, schedule, update on device scalars)
+FTC_OPTIM_AMP_ABI_VERSION = 1
+RADAM_MAX_GROUPS = 16
+OPTIM_AMP_EXPORTS = ["ftc_optim_amp_abi_version", "ftc_amp_nonfinite_scan", "ftc_radam_sf_schedule", "ftc_radam_schedulefree_step_dev"]
 
 
 # include/ftc_ocr.h (page-level OCR glue): again its own version and list
@@ -144,6 +148,23 @@ class OpInfo(C.Structure):
 
 class MtChunk(C.Structure):
     _fields_ = [("y", C.c_void_p), ("g", C.c_void_p), ("v", C.c_void_p), ("z", C.c_void_p), ("n", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RadamHyper(C.Structure):
+    """ftc_radam_hyper of include/ftc_optim_amp.h: 56 bytes."""
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [
+        (n, C.c_int32) for n in ("r", "weight_lr_power", "silent_sgd_phase", "reserved")]
+
+
+class RadamSchedState(C.Structure):
+    """ftc_radam_sched_state of include/ftc_optim_amp.h: 32 bytes."""
+    _fields_ = [("k", C.c_int64), ("lr_max", C.c_double), ("weight_sum", C.c_double), ("scheduled_lr", C.c_double)]
+
+
+class RadamScalars(C.Structure):
+    """ftc_radam_scalars of include/ftc_optim_amp.h: 48 bytes."""
+    _fields_ = [(n, C.c_float) for n in ("beta2", "one_minus_beta2", "bias_correction2", "eps", "weight_decay", "ckp1", "y_alpha", "lr", "inv_scale")] + [
+        (n, C.c_int32) for n in ("adam", "skip", "reserved")]
 
 
 class PackEntry(C.Structure):
@@ -331,6 +352,10 @@ def load():
     lib.ftc_optim_abi_version.restype = i32
     lib.ftc_radam_schedulefree_step.argtypes = [vp, i32, i32] + [C.c_float] * 8 + [i32, vp]
     lib.ftc_schedulefree_lerp.argtypes = [vp, i32, C.c_float, vp]
+    lib.ftc_optim_amp_abi_version.restype = i32
+    lib.ftc_amp_nonfinite_scan.argtypes = [vp, i32, vp, vp]
+    lib.ftc_radam_sf_schedule.argtypes = [C.POINTER(RadamHyper), i32, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.ftc_radam_schedulefree_step_dev.argtypes = [vp, i32, vp, i32, vp]
     lib.ftc_ocr_abi_version.restype = i32
     lib.ftc_ocr_assemble.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp, vp]
     lib.ftc_prep_abi_version.restype = i32
@@ -362,6 +387,8 @@ def load():
         raise FtcLibraryError(f"OCR ABI mismatch: library {lib.ftc_ocr_abi_version()} vs binding {FTC_OCR_ABI_VERSION}")
     if lib.ftc_optim_abi_version() != FTC_OPTIM_ABI_VERSION:
         raise FtcLibraryError(f"optimizer ABI mismatch: library {lib.ftc_optim_abi_version()} vs binding {FTC_OPTIM_ABI_VERSION}")
+    if lib.ftc_optim_amp_abi_version() != FTC_OPTIM_AMP_ABI_VERSION:
+        raise FtcLibraryError(f"optimizer AMP ABI mismatch: library {lib.ftc_optim_amp_abi_version()} vs binding {FTC_OPTIM_AMP_ABI_VERSION}")
     if lib.ftc_text_attention16_abi_version() != FTC_TEXT_ATTENTION16_ABI_VERSION:
         raise FtcLibraryError(f"text attention16 ABI mismatch: library {lib.ftc_text_attention16_abi_version()} vs binding {FTC_TEXT_ATTENTION16_ABI_VERSION}")
     if lib.ftc_text_attention_f16_abi_version() != FTC_TEXT_ATTENTION_F16_ABI_VERSION:

@@ -24,7 +24,8 @@ TUNING_INC = os.path.join(CSRC, "build", "tuning_table.inc")       # generated: 
 MODEL_NET_H = os.path.join(CSRC, "model_net.h")
 TEXT_BWD_H = os.path.join(os.path.dirname(HERE), "include", "ftc_text_bwd.h")      # the recognizer's backward kernels and loss: three sources of their own
 EXTRA_DEPS.update({"text_attention_bwd.hip": [TEXT_BWD_H], "text_ops_bwd.hip": [TEXT_BWD_H], "text_loss.hip": [TEXT_BWD_H]})
-EXTRA_DEPS.update({"optim_radam.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_optim.h")]})      # RAdamScheduleFree and the train() / eval() swap
+EXTRA_DEPS.update({"optim_radam.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_optim.h"),
+                                       os.path.join(os.path.dirname(HERE), "include", "ftc_optim_amp.h")]})      # RAdamScheduleFree, the train() / eval() swap, the device schedule and AMP step
 EXTRA_DEPS.update({"text_linear.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_text_linear.h"),
                                        os.path.join(CSRC, "text_linear_choice.h")]})      # the recognizer's linear layers: one source, its choice header
 EXTRA_DEPS.update({"text_linear_f16.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_text_linear_f16.h"),

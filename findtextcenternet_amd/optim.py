@@ -8,11 +8,13 @@ it unchanged.  ``step()`` is one HIP launch over all parameters of a group (``ft
 
 ``RAdamScheduleFree`` is the same for the text recognizer (the reference's ``models/radam_schedulefree.py``, ``train3.py:120-121``):
 ``radam_step_scalars`` is its float64 schedule, ``step()`` one ``ftc_radam_schedulefree_step`` launch per group and ``train()`` /
-``eval()`` one ``ftc_schedulefree_lerp`` launch per group (``include/ftc_optim.h``).
+``eval()`` one ``ftc_schedulefree_lerp`` launch per group (``include/ftc_optim.h``).  With ``schedule="device"`` the schedule lives on the GPU
+and the step unscales, checks and skips there (``include/ftc_optim_amp.h``); ``AmpScaler`` is the loss scaler for that mode.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
@@ -72,6 +74,16 @@ def radam_step_scalars(group: dict) -> Dict[str, float]:
             "weight_decay": group["weight_decay"], "ckp1": ckp1, "y_alpha": lr * (beta1 * (1 - ckp1) - 1), "lr": lr}
 
 
+def _device_powers(group: dict) -> Tuple[int, int]:
+    """(r, weight_lr_power) of a group as the integers the device schedule raises to (include/ftc_optim_amp.h: exponentiation by squaring)."""
+    out = []
+    for key in ("r", "weight_lr_power"):
+        v = group[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0 or float(v) != int(v) or v > 2 ** 31 - 1:
+            raise ValueError(f"findtextcenternet_amd.RAdamScheduleFree: schedule='device' takes {key} only as a non-negative integer value "
+                             f"(got {v!r}); schedule='host' takes it")
+        out.append(int(v))
+    return out[0], out[1]
 
 
 _NOT_TRAIN = ("Optimizer was not in train mode when step is called. Please insert .train() and .eval() calls on the "
@@ -187,18 +199,153 @@ class RAdamScheduleFree(_MultiTensorOptimizer):
     ``step()`` is one HIP launch per group (``ftc_radam_schedulefree_step``) in place of up to ten ``torch._foreach_*`` passes, ``train()`` /
     ``eval()`` one launch per group (``ftc_schedulefree_lerp``) in place of one ``lerp_`` per tensor.  ``foreach`` is accepted and ignored.
 
-    The schedule (``radam_step_scalars``) lives on the host, so the optimizer does NOT claim ``_step_supports_amp_scaling``:
-    ``torch.amp.GradScaler`` takes its generic path -- unscale, read the found-inf flag, skip ``step()`` altogether -- which is what it does
-    with the reference, and ``k``, ``lr_max`` and ``weight_sum`` stay where they were when a step is skipped."""
+    ``schedule="host"`` (the default): the schedule (``radam_step_scalars``) lives on the host, so the optimizer does NOT claim
+    ``_step_supports_amp_scaling``: ``torch.amp.GradScaler`` takes its generic path -- unscale, read the found-inf flag, skip ``step()``
+    altogether -- which is what it does with the reference, and ``k``, ``lr_max`` and ``weight_sum`` stay where they were when a step is skipped.
+
+    ``schedule="device"``: ``k``, ``lr_max``, ``weight_sum`` and ``scheduled_lr`` of every group live in device memory and one small float64 launch
+    advances them (``ftc_radam_sf_schedule``, the exact-operation contract of ``include/ftc_optim_amp.h``; ``tests/radam_device_operands.py`` restates
+    it in Python).  The instance sets ``_step_supports_amp_scaling``: ``step()`` reads the ``grad_scale`` / ``found_inf`` tensors that
+    ``torch.amp.GradScaler.step`` (or ``AmpScaler.step``) attaches, multiplies the gradients by ``1 / grad_scale`` inside the update and skips the
+    whole step -- parameters, state and schedule, all groups -- on the device where a gradient is not finite.  No ``.item()``, no host
+    synchronisation, no allocation after the first step: the step can be captured into a HIP graph.  Without ``grad_scale`` and ``found_inf`` a plain
+    ``step()`` behaves as in host mode (an infinite gradient gives NaN, nothing is skipped).  ``r`` and ``weight_lr_power`` must be non-negative
+    integer values.  In this mode ``group["k"]``, ``["lr_max"]``, ``["weight_sum"]`` and ``["scheduled_lr"]`` are MIRRORS that are stale between
+    syncs: ``sync_schedule()`` reads them back (one device-to-host copy), ``state_dict()`` does so first, so a checkpoint moves either way between
+    host mode, device mode and the reference; ``load_state_dict``, unpickling and ``deepcopy`` upload the host values again on the next ``step()``.
+    One difference to the generic path: on a skipped step the gradients are left as they are -- still scaled, not overwritten -- where
+    ``GradScaler``'s generic path leaves them unscaled."""
 
     def __init__(self, params, lr=0.0025, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0,
                  r: float = 0.0, weight_lr_power: float = 2.0, foreach: Optional[bool] = hasattr(torch, "_foreach_mul_"),
-                 silent_sgd_phase: bool = True):
+                 silent_sgd_phase: bool = True, schedule: str = "host"):
         if isinstance(lr, torch.Tensor):
             raise TypeError("findtextcenternet_amd.RAdamScheduleFree: lr must be a float (the schedule is computed on the host)")
+        if schedule not in ("host", "device"):
+            raise ValueError(f"findtextcenternet_amd.RAdamScheduleFree: schedule must be 'host' or 'device', not {schedule!r}")
         defaults = dict(lr=lr, betas=betas, eps=eps, r=r, k=0, train_mode=False, weight_sum=0.0, lr_max=-1.0, scheduled_lr=0.0,
                         weight_lr_power=weight_lr_power, weight_decay=weight_decay, foreach=foreach, silent_sgd_phase=silent_sgd_phase)
         super().__init__(params, defaults)
+        self._schedule = schedule
+        if schedule == "device":
+            self._step_supports_amp_scaling = True
+            for group in self.param_groups:
+                _device_powers(group)
+            if len(self.param_groups) > L.RADAM_MAX_GROUPS:
+                raise ValueError(f"findtextcenternet_amd.RAdamScheduleFree: schedule='device' takes at most {L.RADAM_MAX_GROUPS} parameter groups "
+                                 "(schedule='host' takes any number)")
+
+    # ---- schedule="device": the state block, its mirrors, and what survives a copy ---------------------------------------------------------------
+    def __getstate__(self):
+        self.sync_schedule()
+        return dict(super().__getstate__(), _schedule=self.__dict__.get("_schedule", "host"))
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.__dict__.setdefault("_schedule", "host")
+        self.__dict__.pop("_block", None)                # the copy's device schedule is made from its (synced) host values on its next step()
+        if self._schedule == "device":
+            self._step_supports_amp_scaling = True
+
+    def sync_schedule(self) -> None:
+        """schedule="device": reads k, lr_max, weight_sum and scheduled_lr of every group back into ``param_groups`` -- one device-to-host copy,
+        which waits for the device.  A no-op in host mode and before the first step."""
+        block = self.__dict__.get("_block")
+        if block is None or block["stale"]:
+            return
+        n = len(self.param_groups)
+        raw = block["buf"][:n * C.sizeof(L.RadamSchedState)].cpu().numpy().tobytes()
+        for st, group in zip((L.RadamSchedState * n).from_buffer_copy(raw), self.param_groups):
+            group["k"], group["lr_max"], group["weight_sum"], group["scheduled_lr"] = int(st.k), float(st.lr_max), float(st.weight_sum), float(st.scheduled_lr)
+
+    def state_dict(self):
+        self.sync_schedule()
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict) -> None:
+        super().load_state_dict(state_dict)
+        block = self.__dict__.get("_block")
+        if block is not None:
+            block["stale"] = True
+
+    def add_param_group(self, param_group) -> None:
+        self.sync_schedule()                             # the new group's state is uploaded with the others', from the host values
+        super().add_param_group(param_group)
+        block = self.__dict__.get("_block")
+        if block is not None:
+            block["stale"] = True
+
+    def _device_block(self, dev: torch.device, n_chunks: int) -> dict:
+        """One uint8 device buffer: 16 schedule states, 16 scalar blocks, the found-inf float, then one uint32 flag per chunk.  Made on the first
+        step (and again when the chunk count grows or the device changes); the states are uploaded from param_groups whenever they are stale."""
+        n_state, n_scal = L.RADAM_MAX_GROUPS * C.sizeof(L.RadamSchedState), L.RADAM_MAX_GROUPS * C.sizeof(L.RadamScalars)
+        block = self.__dict__.get("_block")
+        if block is not None and (block["buf"].device != dev or block["n_chunks"] < n_chunks):
+            self.sync_schedule()
+            block = None
+        if block is None:
+            buf = torch.zeros(n_state + n_scal + 16 + 4 * n_chunks, dtype=torch.uint8, device=dev)
+            base = buf.data_ptr()
+            block = self.__dict__["_block"] = dict(buf=buf, n_chunks=n_chunks, stale=True, state=base, scalars=base + n_state,
+                                                   found=base + n_state + n_scal, flags=base + n_state + n_scal + 16)
+        if block["stale"]:
+            n = len(self.param_groups)
+            arr = (L.RadamSchedState * n)()
+            for st, group in zip(arr, self.param_groups):
+                st.k, st.lr_max, st.weight_sum, st.scheduled_lr = int(group["k"]), group["lr_max"], group["weight_sum"], group["scheduled_lr"]
+            block["buf"][:C.sizeof(arr)].copy_(torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8))
+            block["stale"] = False
+        return block
+
+    @staticmethod
+    def _amp_scalar(t, name: str, dev: torch.device) -> int:
+        if t is None:
+            return 0
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.numel() == 1 and t.device == dev):
+            raise TypeError(f"findtextcenternet_amd.RAdamScheduleFree: {name} must be a one-element fp32 tensor on the parameters' device")
+        return t.data_ptr()
+
+    def _step_device(self) -> None:
+        lib = L.load()
+        groups = self.param_groups
+        if not 1 <= len(groups) <= L.RADAM_MAX_GROUPS:
+            raise ValueError(f"findtextcenternet_amd.RAdamScheduleFree: schedule='device' takes 1 .. {L.RADAM_MAX_GROUPS} parameter groups")
+        hyper = (L.RadamHyper * len(groups))()
+        for h, group in zip(hyper, groups):
+            h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+            h.r, h.weight_lr_power = _device_powers(group)
+            h.silent_sgd_phase = int(bool(group["silent_sgd_phase"]))
+        actives = [self._active(group) for group in groups]
+        first = next((a[0] for a in actives if a), None)
+        if first is None:
+            raise RuntimeError("findtextcenternet_amd.RAdamScheduleFree: schedule='device' needs at least one parameter with a gradient "
+                               "(the schedule lives on the parameters' device)")
+        dev = first.device
+        if any(p.device != dev for a in actives for p in a):
+            raise RuntimeError("findtextcenternet_amd.RAdamScheduleFree: schedule='device' needs all parameters on one device")
+        with torch.cuda.device(dev):
+            tables = [self._chunk_table(gi, a) if a else (None, 0) for gi, a in enumerate(actives)]
+            total = sum(n for _, n in tables)
+            block = self._device_block(dev, total)
+            scale = self._amp_scalar(getattr(self, "grad_scale", None), "grad_scale", dev)
+            found_in = self._amp_scalar(getattr(self, "found_inf", None), "found_inf", dev)
+            found_out = self._amp_scalar(getattr(self, "found_inf_out", None), "found_inf_out", dev) or block["found"]
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            scan = bool(scale) and not found_in               # nobody has looked at the scaled gradients yet: the project's own scan does
+            if scan:
+                off = 0
+                for table, n in tables:
+                    if n:
+                        L.check(lib.ftc_amp_nonfinite_scan(table.data_ptr(), n, block["flags"] + 4 * off, stream), "ftc_amp_nonfinite_scan")
+                        off += n
+            L.check(lib.ftc_radam_sf_schedule(hyper, len(groups), block["flags"] if scan else None, total if scan else 0, found_in or None,
+                                              scale or None, block["state"], block["scalars"], found_out, stream), "ftc_radam_sf_schedule")
+            for gi, (table, n) in enumerate(tables):
+                if n:
+                    L.check(lib.ftc_radam_schedulefree_step_dev(table.data_ptr(), n, block["scalars"] + gi * C.sizeof(L.RadamScalars), 1, stream),
+                            "ftc_radam_schedulefree_step_dev")
+        for a in actives:
+            bump_versions(a)                         # on a skipped step nothing was written; the bump is harmless
 
     # x = the averaged iterate (evaluation / checkpoints), y = where gradients are taken (training): p holds one or the other
     @torch.no_grad()
@@ -236,6 +383,9 @@ class RAdamScheduleFree(_MultiTensorOptimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.__dict__.get("_schedule", "host") == "device":
+            self._step_device()
+            return loss
         lib = L.load()
         for gi, group in enumerate(self.param_groups):
             sc = radam_step_scalars(group)
@@ -252,3 +402,67 @@ class RAdamScheduleFree(_MultiTensorOptimizer):
                 bump_versions(active)                # the kernel wrote through raw pointers: tell whoever fingerprints the parameters
             group["k"] = group["k"] + 1
         return loss
+
+
+class AmpScaler:
+    """The loss scaler of the loop that wants no torch pass over the gradients: ``torch.amp.GradScaler``'s protocol and growth rule on top of
+    ``RAdamScheduleFree(..., schedule="device")``'s own scan.
+
+        scaler.scale(loss).backward()        # or TextGrad.forward_backward(..., grad_scale=scaler.scale_tensor)
+        scaler.step(opt); scaler.update()
+
+    ``step(opt)`` hands the optimizer ``scale_tensor`` and no ``found_inf``, so ``opt.step()`` runs ``ftc_amp_nonfinite_scan`` over the scaled
+    gradients, unscales inside the update, skips on the device and leaves the combined flag in this scaler's found-inf tensor;  ``update()`` is one
+    ``torch._amp_update_scale_`` on the three tensors -- torch's rule, not restated.  Nothing here reads the device except ``get_scale()`` and
+    ``state_dict()``.  One scaler serves one optimizer per iteration.  As in the optimizer, the gradients of a skipped step stay scaled."""
+
+    def __init__(self, init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5, growth_interval: int = 2000,
+                 device="cuda"):
+        if growth_factor <= 1.0 or backoff_factor >= 1.0:
+            raise ValueError("findtextcenternet_amd.AmpScaler: growth_factor must be > 1 and backoff_factor < 1")
+        self._growth_factor, self._backoff_factor, self._growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("findtextcenternet_amd.AmpScaler: the scale lives on the GPU (no CPU fallback)")
+        self.scale_tensor = torch.full((), float(init_scale), dtype=torch.float32, device=dev)
+        self._growth_tracker = torch.zeros((), dtype=torch.int32, device=dev)
+        self._found_inf = torch.zeros((), dtype=torch.float32, device=dev)
+        self._stepped = False
+
+    def scale(self, loss: torch.Tensor) -> torch.Tensor:
+        return loss * self.scale_tensor
+
+    def step(self, optimizer, *args, **kwargs):
+        if getattr(optimizer, "_schedule", "host") != "device":
+            raise TypeError("findtextcenternet_amd.AmpScaler.step: needs RAdamScheduleFree(..., schedule='device') "
+                            "(torch.amp.GradScaler drives a host-schedule optimizer)")
+        if self._stepped:
+            raise RuntimeError("findtextcenternet_amd.AmpScaler.step: step() has already been called since the last update()")
+        optimizer.grad_scale, optimizer.found_inf, optimizer.found_inf_out = self.scale_tensor, None, self._found_inf
+        try:
+            out = optimizer.step(*args, **kwargs)
+        finally:
+            del optimizer.grad_scale, optimizer.found_inf, optimizer.found_inf_out
+        self._stepped = True
+        return out
+
+    def update(self) -> None:
+        if not self._stepped:
+            raise RuntimeError("findtextcenternet_amd.AmpScaler.update: no step() since the last update()")
+        torch._amp_update_scale_(self.scale_tensor, self._growth_tracker, self._found_inf, self._growth_factor, self._backoff_factor,
+                                 self._growth_interval)
+        self._stepped = False
+
+    def get_scale(self) -> float:
+        """The current scale as a float: this synchronises."""
+        return float(self.scale_tensor.item())
+
+    def state_dict(self) -> dict:
+        return {"scale": self.get_scale(), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": int(self._growth_tracker.item())}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        self.scale_tensor.fill_(float(state_dict["scale"]))
+        self._growth_tracker.fill_(int(state_dict["_growth_tracker"]))
+        self._growth_factor, self._backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self._growth_interval = int(state_dict["growth_interval"])

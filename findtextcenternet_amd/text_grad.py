@@ -476,11 +476,12 @@ class TextGrad:
             y, yq = rownorm(a=self._ff(p + ".ff", y2), b=skip, gamma=g3, beta=b3, pos_out=nxt)
         return [self._lin(y, P[f"decoder.out_layers.{j}.weight"], P[f"decoder.out_layers.{j}.bias"]) for j in range(3)]
 
-    def forward_backward(self, enc_input: torch.Tensor, dec_input: torch.Tensor, label_code: torch.Tensor, grad_scale: float = 1.0):
+    def forward_backward(self, enc_input: torch.Tensor, dec_input: torch.Tensor, label_code: torch.Tensor, grad_scale=1.0):
         """One training step's forward and backward: the loss dict of ``loss_function3(model(enc_input, dec_input), label_code,
-        dec_input == decoder_MSK)`` (detached) and ``.grad`` = d(grad_scale * loss) / d(parameter) on every device parameter."""
+        dec_input == decoder_MSK)`` (detached) and ``.grad`` = d(grad_scale * loss) / d(parameter) on every device parameter.  grad_scale is a
+        float or a 0-d device tensor (``AmpScaler.scale_tensor``, ``GradScaler``'s scale): a tensor is multiplied in as it is, with no host read."""
         self.zero_grad()
         outs = self.logits(enc_input, dec_input)
         res = loss_function3(outs, label_code.to(outs[0].device), dec_input.to(outs[0].device) == MASK_TOKEN)
-        (res["loss"] * float(grad_scale)).backward()
+        (res["loss"] * (grad_scale if isinstance(grad_scale, torch.Tensor) else float(grad_scale))).backward()
         return {k: v.detach() for k, v in res.items()}

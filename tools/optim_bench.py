@@ -8,6 +8,16 @@
   adamw_fused    ftc_adamw_schedulefree_step over the same table: the same eight fp32 streams per element, the yardstick for the new kernel;
   swap_fused     ftc_schedulefree_lerp, one launch;      swap_lerp   416 lerp_ calls, one per tensor (what the reference's train() / eval() issue).
 
+and the device-resident schedule with its fused AMP step (include/ftc_optim_amp.h):
+
+  amp_scan       ftc_amp_nonfinite_scan over the same table (reads the gradients once: 4 bytes per element);
+  amp_schedule   ftc_radam_sf_schedule, one workgroup: the OR of one flag per chunk and the float64 schedule of the group;
+  radam_step_dev ftc_radam_schedulefree_step_dev: radam_fused with its scalars read from the device (inv_scale = 1, skip = 0), yardstick radam_fused;
+  loop_host_gradscaler / loop_device_gradscaler / loop_device_ampscaler
+                 `scaler.step(opt); scaler.update()` on the class: schedule="host" under torch.amp.GradScaler (its generic path: unscale pass,
+                 found_inf.item(), then step()), schedule="device" under torch.amp.GradScaler (torch's check pass, no host read), schedule="device"
+                 under AmpScaler (the project's scan, no torch pass over the gradients, no host read).
+
 Method as tools/text_bwd_bench.py: warm-up rounds, then ``--repeats`` rounds in which every variant runs once, alternating in one process, the device
 synchronised inside every timed window; medians and the run-to-run spread ((max - min) / median).
 
@@ -121,9 +131,55 @@ def variants(dev):
             for y, z in zip(ys, zs):
                 y.lerp_(end=z, weight=w)
 
+    # include/ftc_optim_amp.h: one block of [state | scalars | found | flags], the schedule placed at the same step
+    block = torch.zeros(32 + 48 + 16 + 4 * n_rows, dtype=torch.uint8, device=dev)
+    state0 = (L.RadamSchedState * 1)()
+    state0[0].k, state0[0].lr_max, state0[0].weight_sum, state0[0].scheduled_lr = STEP - 1, -1.0, 0.0, 0.0
+    block[:32].copy_(torch.frombuffer(bytearray(bytes(state0)), dtype=torch.uint8))
+    b_state, b_scal, b_found, b_flags = (block.data_ptr() + o for o in (0, 32, 80, 96))
+    hyper = (L.RadamHyper * 1)()
+    hyper[0].lr, hyper[0].beta1, hyper[0].beta2, hyper[0].eps, hyper[0].weight_decay = LR, BETAS[0], BETAS[1], EPS, DECAY
+    hyper[0].r, hyper[0].weight_lr_power, hyper[0].silent_sgd_phase = 0, 2, 1
+
+    def amp_scan():
+        L.check(lib.ftc_amp_nonfinite_scan(table.data_ptr(), n_rows, b_flags, st), "ftc_amp_nonfinite_scan")
+
+    def amp_schedule():
+        L.check(lib.ftc_radam_sf_schedule(hyper, 1, b_flags, n_rows, None, None, b_state, b_scal, b_found, st), "ftc_radam_sf_schedule")
+
+    amp_scan()
+    amp_schedule()                                                   # the scalar block of step STEP: adam = 1, inv_scale = 1, skip = 0
+    torch.cuda.synchronize()
+    got = L.RadamScalars.from_buffer_copy(block[32:80].cpu().numpy().tobytes())
+    assert (got.adam, got.skip, got.inv_scale) == (1, 0, 1.0) and got.lr == f(rs["lr"]).value, (got.adam, got.skip, got.inv_scale, got.lr)
+
+    def radam_step_dev():
+        L.check(lib.ftc_radam_schedulefree_step_dev(table.data_ptr(), n_rows, b_scal, 1, st), "ftc_radam_schedulefree_step_dev")
+
+    # the three loops: the classes on the same tensors; the device-mode instance serves both of its scalers in turn
+    opt_dev = O.RAdamScheduleFree(ps, lr=LR, betas=BETAS, eps=EPS, weight_decay=DECAY, schedule="device")
+    for p, v, z in zip(ps, vs, zs):
+        opt_dev.state[p]["z"], opt_dev.state[p]["exp_avg_sq"] = z, v
+    opt_dev.param_groups[0].update(k=STEP - 1, train_mode=True)
+    scalers = {"loop_host_gradscaler": (torch.amp.GradScaler("cuda", init_scale=65536.0, growth_interval=10 ** 9), opt),
+               "loop_device_gradscaler": (torch.amp.GradScaler("cuda", init_scale=65536.0, growth_interval=10 ** 9), opt_dev),
+               "loop_device_ampscaler": (O.AmpScaler(init_scale=65536.0, growth_interval=10 ** 9), opt_dev)}
+    for sc, _ in scalers.values():
+        sc.scale(torch.zeros(1, device=dev))                         # GradScaler makes its scale tensor on the first scale(loss)
+
+    def loop(name):
+        sc, o = scalers[name]
+
+        def run():
+            sc.step(o)
+            sc.update()
+        return run
+
     n = sum(math.prod(s) for s in shapes)
-    return {"radam_fused": radam_fused, "radam_class": opt.step, "radam_foreach": radam_foreach, "adamw_fused": adamw_fused, "swap_fused": swap_fused,
-            "swap_lerp": swap_lerp}, n, len(shapes), n_rows
+    out = {"radam_fused": radam_fused, "radam_class": opt.step, "radam_foreach": radam_foreach, "adamw_fused": adamw_fused, "swap_fused": swap_fused,
+           "swap_lerp": swap_lerp, "amp_scan": amp_scan, "amp_schedule": amp_schedule, "radam_step_dev": radam_step_dev}
+    out.update({name: loop(name) for name in scalers})
+    return out, n, len(shapes), n_rows
 
 
 def main():
@@ -151,6 +207,24 @@ def main():
     res["swap_fused_gbs"] = round(n * 4 * 3 / (statistics.median(times["swap_fused"]) * 1e-3) / 1e9, 1)
     r, w = times["radam_fused"], times["adamw_fused"]
     res["radam_at_adamw_rate_within_spreads"] = bool(abs(statistics.median(r) - statistics.median(w)) <= (max(r) - min(r)) + (max(w) - min(w)))
+    res["radam_step_dev_gbs"] = round(n * 4 * 8 / (statistics.median(times["radam_step_dev"]) * 1e-3) / 1e9, 1)
+    res["amp_scan_gbs"] = round(n * 4 / (statistics.median(times["amp_scan"]) * 1e-3) / 1e9, 1)             # the gradients, read once
+    d = times["radam_step_dev"]
+    res["step_dev_at_radam_rate_within_spreads"] = bool(abs(statistics.median(d) - statistics.median(r)) <= (max(d) - min(d)) + (max(r) - min(r)))
+    # In the round the two update kernels follow different launches (what the caches hold differs by what ran before).  The pair again, each
+    # timed directly behind the same predecessor -- one pass of the scan over the gradients:
+    paired = {"radam_fused": [], "radam_step_dev": []}
+    for it in range(a.warmup + a.repeats):
+        for k in paired:
+            vs["amp_scan"]()
+            ms = timed(vs[k])
+            if it >= a.warmup:
+                paired[k].append(ms)
+    for k, ts in paired.items():
+        res[f"paired_{k}_ms"] = round(statistics.median(ts), 4)
+        res[f"paired_{k}_spread"] = round((max(ts) - min(ts)) / statistics.median(ts), 4)
+    pr, pd = paired["radam_fused"], paired["radam_step_dev"]
+    res["paired_step_dev_at_radam_rate_within_spreads"] = bool(abs(statistics.median(pd) - statistics.median(pr)) <= (max(pd) - min(pd)) + (max(pr) - min(pr)))
     line = json.dumps(res)
     print(line)
     if a.json:
