@@ -61,6 +61,10 @@ TEXT_LINEAR_EXPORTS = ["ftc_text_linear_abi_version", "ftc_text_linear", "ftc_te
 # include/ftc_text_linear_f16.h (the same calls on operands rounded to fp16 as they are staged: v_mfma_f32_32x32x16_f16, fp32 sums)
 FTC_TEXT_LINEAR_F16_ABI_VERSION = 1
 TEXT_LINEAR_F16_EXPORTS = ["ftc_text_linear_f16_abi_version", "ftc_text_linear_f16", "ftc_text_linear_f16_bwd_workspace_bytes", "ftc_text_linear_f16_bwd"]
+# include/ftc_text_linear_res.h (the residual forms of both: y = (x w^T + bias) + res, dx = dy w + dx_add)
+FTC_TEXT_LINEAR_RES_ABI_VERSION = 1
+TEXT_LINEAR_RES_EXPORTS = ["ftc_text_linear_res_abi_version", "ftc_text_linear_res", "ftc_text_linear_f16_res", "ftc_text_linear_bwd_add",
+                           "ftc_text_linear_f16_bwd_add"]
 # include/ftc_text_attention_f16.h (fused attention, forward and backward, on operands rounded to fp16: the training path, no kv_row form)
 FTC_TEXT_ATTENTION_F16_ABI_VERSION = 1
 TEXT_ATTENTION_F16_EXPORTS = ["ftc_text_attention_f16_abi_version", "ftc_text_attention_f16", "ftc_text_attention_f16_bwd_workspace_bytes",
@@ -340,6 +344,11 @@ def load():
     lib.ftc_text_linear_f16_bwd_workspace_bytes.argtypes = [i64, i32, i32]
     lib.ftc_text_linear_f16_bwd_workspace_bytes.restype = i64
     lib.ftc_text_linear_f16_bwd.argtypes = lib.ftc_text_linear_bwd.argtypes
+    lib.ftc_text_linear_res_abi_version.restype = i32
+    lib.ftc_text_linear_res.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i32, i32, vp]
+    lib.ftc_text_linear_f16_res.argtypes = lib.ftc_text_linear_res.argtypes
+    lib.ftc_text_linear_bwd_add.argtypes = [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp]
+    lib.ftc_text_linear_f16_bwd_add.argtypes = lib.ftc_text_linear_bwd_add.argtypes
     lib.ftc_text_attention_f16_abi_version.restype = i32
     lib.ftc_text_attention_f16.argtypes = lib.ftc_text_attention.argtypes
     lib.ftc_text_attention_f16_bwd_workspace_bytes.argtypes = [i32, i32, i32, i32]
@@ -393,6 +402,8 @@ def load():
         raise FtcLibraryError(f"text attention16 ABI mismatch: library {lib.ftc_text_attention16_abi_version()} vs binding {FTC_TEXT_ATTENTION16_ABI_VERSION}")
     if lib.ftc_text_attention_f16_abi_version() != FTC_TEXT_ATTENTION_F16_ABI_VERSION:
         raise FtcLibraryError(f"text attention fp16 ABI mismatch: library {lib.ftc_text_attention_f16_abi_version()} vs binding {FTC_TEXT_ATTENTION_F16_ABI_VERSION}")
+    if lib.ftc_text_linear_res_abi_version() != FTC_TEXT_LINEAR_RES_ABI_VERSION:
+        raise FtcLibraryError(f"text linear residual ABI mismatch: library {lib.ftc_text_linear_res_abi_version()} vs binding {FTC_TEXT_LINEAR_RES_ABI_VERSION}")
     if lib.ftc_text_linear_f16_abi_version() != FTC_TEXT_LINEAR_F16_ABI_VERSION:
         raise FtcLibraryError(f"text linear fp16 ABI mismatch: library {lib.ftc_text_linear_f16_abi_version()} vs binding {FTC_TEXT_LINEAR_F16_ABI_VERSION}")
     if lib.ftc_text_linear_abi_version() != FTC_TEXT_LINEAR_ABI_VERSION:

@@ -27,6 +27,7 @@
 #include "ftc_common.h"
 #include "ftc_host.h"
 #include "text_linear_choice.h"
+#include "../../include/ftc_text_linear_res.h"
 
 namespace {
 
@@ -42,6 +43,8 @@ struct GemmArgs {
     float* C;
     int64_t ldc, c_chunk;           // pitch of C; floats between the C of consecutive chunks (blockIdx.z)
     const float* bias;              // added to the finished chain, per column of C (forward)
+    const float* res;               // RES kernels only: [M][N] at pitch ldres, added per element after the bias (ftc_text_linear_res.h)
+    int64_t ldres;
     float* colsum;                  // sums over the reduction of A's columns (weight gradient: dbias) ...
     int64_t colsum_chunk;           // ... and floats between consecutive chunks' sums
     int64_t M, N, R;                // extent of C, length of the whole reduction
@@ -92,7 +95,7 @@ __device__ __forceinline__ void stage_tile(float* __restrict__ S, int t, const f
     }
 }
 
-template <bool AKC, bool BKC, int TM, int TN>
+template <bool AKC, bool BKC, int TM, int TN, bool RES>
 __global__ __launch_bounds__(256) void text_linear_kernel(GemmArgs g) {
     __shared__ __attribute__((aligned(16))) float As[TL_BK * pitch_mc(TM)];
     __shared__ __attribute__((aligned(16))) float Bs[TL_BK * pitch_mc(TN)];
@@ -158,7 +161,10 @@ __global__ __launch_bounds__(256) void text_linear_kernel(GemmArgs g) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int64_t row = m0 + wm + 32 * im + (e & 3) + 8 * (e >> 2) + 4 * h;
-                    if (row < g.M) C[row * g.ldc + col] = g.bias ? acc[im][in][e] + b : acc[im][in][e];
+                    if (row >= g.M) continue;
+                    const float v = g.bias ? acc[im][in][e] + b : acc[im][in][e];
+                    if constexpr (RES) C[row * g.ldc + col] = v + g.res[row * g.ldres + col];          // one more fp32 addition, after the bias
+                    else C[row * g.ldc + col] = v;
                 }
             }
     }
@@ -179,10 +185,17 @@ int hip_rc(hipError_t e, const char* what) {
     return e == hipSuccess ? FTC_OK : ftc_set_error(FTC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// g.res selects the residual instantiation; without it the kernel is the one it always was
 template <bool AKC, bool BKC>
 void launch(const GemmArgs& g, const LinearLaunch& l, hipStream_t s) {
     const dim3 grid(l.grid[0], l.grid[1], l.grid[2]);
-    hipLaunchKernelGGL((text_linear_kernel<AKC, BKC, TL_WG, TL_WG>), grid, dim3(256), 0, s, g);
+    if constexpr (AKC) {          // y and dx; the weight gradient has no residual form
+        if (g.res) {
+            hipLaunchKernelGGL((text_linear_kernel<AKC, BKC, TL_WG, TL_WG, true>), grid, dim3(256), 0, s, g);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((text_linear_kernel<AKC, BKC, TL_WG, TL_WG, false>), grid, dim3(256), 0, s, g);
 }
 
 unsigned reduce_grid(int64_t n) {
@@ -190,42 +203,24 @@ unsigned reduce_grid(int64_t n) {
     return (unsigned)(b < (1 << 20) ? b : (1 << 20));
 }
 
-}  // namespace
-
-extern "C" {
-
-int ftc_text_linear_abi_version(void) { return FTC_TEXT_LINEAR_ABI_VERSION; }
-
-int ftc_text_linear(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y, int64_t ldy, int64_t rows, int K, int N,
-                    void* stream) {
-    LinearChoice c;
-    if (const char* why = linear_resolve_fwd(x, ldx, w, ldw, y, ldy, rows, K, N, &c)) return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear: ") + why);
-    if (bias && (uintptr_t)bias % 4) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_linear: a pointer is not aligned to a float");
+int run_fwd(const LinearChoice& c, const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const float* res, int64_t ldres, float* y,
+            int64_t ldy, int64_t rows, int K, int N, void* stream, const char* what) {
     GemmArgs g{};
-    g.A = x; g.lda = ldx; g.B = w; g.ldb = ldw; g.C = y; g.ldc = ldy; g.bias = bias;
+    g.A = x; g.lda = ldx; g.B = w; g.ldb = ldw; g.C = y; g.ldc = ldy; g.bias = bias; g.res = res; g.ldres = ldres;
     g.M = rows; g.N = N; g.R = K; g.chunk = K; g.vec_a = c.vec_x; g.vec_b = c.vec_w; g.mma = 1;
     launch<true, true>(g, c.y, static_cast<hipStream_t>(stream));
-    return hip_rc(hipGetLastError(), "ftc_text_linear");
+    return hip_rc(hipGetLastError(), what);
 }
 
-int64_t ftc_text_linear_bwd_workspace_bytes(int64_t rows, int K, int N) {
-    if (const char* why = linear_dims_refused(rows, K, N)) {
-        ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_bwd_workspace_bytes: ") + why);
-        return -1;
-    }
-    return 4 * linear_workspace_floats(rows, K, N);
-}
-
-int ftc_text_linear_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* dy, int64_t lddy, float* dx, int64_t lddx, float* dw,
-                        int64_t lddw, float* dbias, int64_t rows, int K, int N, void* workspace, void* stream) {
-    LinearChoice c;
-    if (const char* why = linear_resolve_bwd(x, ldx, w, ldw, dy, lddy, dx, lddx, dw, lddw, dbias, rows, K, N, workspace, &c))
-        return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_bwd: ") + why);
+// the launches of a resolved backward call; dx_add (with dx) selects the data gradient's residual form
+int run_bwd(const LinearChoice& c, const float* x, int64_t ldx, const float* w, int64_t ldw, const float* dy, int64_t lddy, float* dx, int64_t lddx,
+            const float* dx_add, int64_t lddxa, float* dw, int64_t lddw, float* dbias, int64_t rows, int K, int N, void* workspace, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dx) {
         GemmArgs g{};
         g.A = dy; g.lda = lddy; g.B = w; g.ldb = ldw; g.C = dx; g.ldc = lddx;
         g.M = rows; g.N = K; g.R = N; g.chunk = N; g.vec_a = c.vec_dy; g.vec_b = c.vec_w; g.mma = 1;
+        g.res = dx_add; g.ldres = lddxa;
         launch<true, false>(g, c.dx, s);
         if (int rc = hip_rc(hipGetLastError(), "ftc_text_linear_bwd: data gradient")) return rc;
     }
@@ -251,6 +246,56 @@ int ftc_text_linear_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw
         }
     }
     return FTC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ftc_text_linear_abi_version(void) { return FTC_TEXT_LINEAR_ABI_VERSION; }
+
+int ftc_text_linear_res_abi_version(void) { return FTC_TEXT_LINEAR_RES_ABI_VERSION; }
+
+int ftc_text_linear(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y, int64_t ldy, int64_t rows, int K, int N,
+                    void* stream) {
+    LinearChoice c;
+    if (const char* why = linear_resolve_fwd(x, ldx, w, ldw, y, ldy, rows, K, N, &c)) return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear: ") + why);
+    if (bias && (uintptr_t)bias % 4) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_linear: a pointer is not aligned to a float");
+    return run_fwd(c, x, ldx, w, ldw, bias, nullptr, 0, y, ldy, rows, K, N, stream, "ftc_text_linear");
+}
+
+int ftc_text_linear_res(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const float* res, int64_t ldres, float* y, int64_t ldy,
+                        int64_t rows, int K, int N, void* stream) {
+    LinearChoice c;
+    if (const char* why = linear_resolve_fwd_res(x, ldx, w, ldw, res, ldres, y, ldy, rows, K, N, &c))
+        return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_res: ") + why);
+    if (bias && (uintptr_t)bias % 4) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_linear_res: a pointer is not aligned to a float");
+    return run_fwd(c, x, ldx, w, ldw, bias, res, ldres, y, ldy, rows, K, N, stream, "ftc_text_linear_res");
+}
+
+int64_t ftc_text_linear_bwd_workspace_bytes(int64_t rows, int K, int N) {
+    if (const char* why = linear_dims_refused(rows, K, N)) {
+        ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_bwd_workspace_bytes: ") + why);
+        return -1;
+    }
+    return 4 * linear_workspace_floats(rows, K, N);
+}
+
+int ftc_text_linear_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* dy, int64_t lddy, float* dx, int64_t lddx, float* dw,
+                        int64_t lddw, float* dbias, int64_t rows, int K, int N, void* workspace, void* stream) {
+    LinearChoice c;
+    if (const char* why = linear_resolve_bwd(x, ldx, w, ldw, dy, lddy, dx, lddx, dw, lddw, dbias, rows, K, N, workspace, &c))
+        return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_bwd: ") + why);
+    return run_bwd(c, x, ldx, w, ldw, dy, lddy, dx, lddx, nullptr, 0, dw, lddw, dbias, rows, K, N, workspace, stream);
+}
+
+int ftc_text_linear_bwd_add(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* dy, int64_t lddy, float* dx, int64_t lddx,
+                            const float* dx_add, int64_t lddxa, float* dw, int64_t lddw, float* dbias, int64_t rows, int K, int N, void* workspace,
+                            void* stream) {
+    LinearChoice c;
+    if (const char* why = linear_resolve_bwd_add(x, ldx, w, ldw, dy, lddy, dx, lddx, dx_add, lddxa, dw, lddw, dbias, rows, K, N, workspace, &c))
+        return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_bwd_add: ") + why);
+    return run_bwd(c, x, ldx, w, ldw, dy, lddy, dx, lddx, dx_add, lddxa, dw, lddw, dbias, rows, K, N, workspace, stream);
 }
 
 }  // extern "C"

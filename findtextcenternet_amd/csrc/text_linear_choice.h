@@ -108,4 +108,21 @@ inline const char* linear_resolve_bwd(const float* x, int64_t ldx, const float* 
     return nullptr;
 }
 
+// The residual forms (include/ftc_text_linear_res.h): the parent's resolve, then the added operand held to the rules of every other.  It is read
+// one float per lane in the store's own pattern, so it takes no part in the 16-byte choice.
+inline const char* linear_resolve_fwd_res(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* res, int64_t ldres, const float* y, int64_t ldy,
+                                          int64_t rows, int K, int N, LinearChoice* c) {
+    if (const char* r = linear_resolve_fwd(x, ldx, w, ldw, y, ldy, rows, K, N, c)) return r;
+    return linear_operand_refused(res, ldres, rows, N);
+}
+
+inline const char* linear_resolve_bwd_add(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* dy, int64_t lddy, const float* dx, int64_t lddx,
+                                          const float* dx_add, int64_t lddxa, const float* dw, int64_t lddw, const float* dbias, int64_t rows, int K, int N,
+                                          const void* workspace, LinearChoice* c) {
+    if (const char* r = linear_dims_refused(rows, K, N)) return r;
+    if (!dx) return dx_add ? "dx_add needs dx" : "a required pointer is NULL";
+    if (const char* r = linear_resolve_bwd(x, ldx, w, ldw, dy, lddy, dx, lddx, dw, lddw, dbias, rows, K, N, workspace, c)) return r;
+    return linear_operand_refused(dx_add, lddxa, rows, K);
+}
+
 }  // namespace textlinear

@@ -30,6 +30,7 @@
 #include "ftc_host.h"
 #include "text_linear_choice.h"
 #include "../../include/ftc_text_linear_f16.h"
+#include "../../include/ftc_text_linear_res.h"
 
 namespace {
 
@@ -46,6 +47,8 @@ struct GemmArgs {
     float* C;
     int64_t ldc, c_chunk;           // pitch of C; floats between the C of consecutive chunks (blockIdx.z)
     const float* bias;              // added to the finished sum, per column of C (forward)
+    const float* res;               // RES kernels only: [M][N] at pitch ldres, added per element after the bias (ftc_text_linear_res.h)
+    int64_t ldres;
     float* colsum;                  // sums over the reduction of A's columns (weight gradient: dbias) ...
     int64_t colsum_chunk;           // ... and floats between consecutive chunks' sums
     int64_t M, N, R;                // extent of C, length of the whole reduction
@@ -107,7 +110,7 @@ __device__ __forceinline__ void stage_tile(_Float16* __restrict__ S, int t, cons
     }
 }
 
-template <bool AKC, bool BKC, int TM, int TN>
+template <bool AKC, bool BKC, int TM, int TN, bool RES>
 __global__ __launch_bounds__(256) void text_linear_f16_kernel(GemmArgs g) {
     static_assert(TM % 64 == 0 && TN % 64 == 0 && TM * HF_BK % 2048 == 0 && TN * HF_BK % 2048 == 0, "whole 32 x 32 tiles per wave, whole passes per thread");
     __shared__ __attribute__((aligned(16))) _Float16 As[TM * HF_PITCH];
@@ -173,7 +176,10 @@ __global__ __launch_bounds__(256) void text_linear_f16_kernel(GemmArgs g) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int64_t row = m0 + wm + 32 * im + (e & 3) + 8 * (e >> 2) + 4 * h;
-                    if (row < g.M) C[row * g.ldc + col] = g.bias ? acc[im][in][e] + b : acc[im][in][e];
+                    if (row >= g.M) continue;
+                    const float v = g.bias ? acc[im][in][e] + b : acc[im][in][e];
+                    if constexpr (RES) C[row * g.ldc + col] = v + g.res[row * g.ldres + col];          // one more fp32 addition, after the bias
+                    else C[row * g.ldc + col] = v;
                 }
             }
     }
@@ -198,7 +204,13 @@ int hip_rc(hipError_t e, const char* what) {
 template <bool AKC, bool BKC>
 void launch(const GemmArgs& g, int64_t chunks, hipStream_t s) {
     const dim3 grid((unsigned)cdiv(g.M, HF_TM), g.mma ? (unsigned)cdiv(g.N, HF_TN) : 1u, (unsigned)chunks);
-    hipLaunchKernelGGL((text_linear_f16_kernel<AKC, BKC, HF_TM, HF_TN>), grid, dim3(256), 0, s, g);
+    if constexpr (AKC) {          // y and dx; the weight gradient has no residual form.  g.res selects it; without it the kernel is the one it always was
+        if (g.res) {
+            hipLaunchKernelGGL((text_linear_f16_kernel<AKC, BKC, HF_TM, HF_TN, true>), grid, dim3(256), 0, s, g);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((text_linear_f16_kernel<AKC, BKC, HF_TM, HF_TN, false>), grid, dim3(256), 0, s, g);
 }
 
 unsigned reduce_grid(int64_t n) {
@@ -206,42 +218,24 @@ unsigned reduce_grid(int64_t n) {
     return (unsigned)(b < (1 << 20) ? b : (1 << 20));
 }
 
-}  // namespace
-
-extern "C" {
-
-int ftc_text_linear_f16_abi_version(void) { return FTC_TEXT_LINEAR_F16_ABI_VERSION; }
-
-int ftc_text_linear_f16(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y, int64_t ldy, int64_t rows, int K, int N,
-                        void* stream) {
-    LinearChoice c;
-    if (const char* why = linear_resolve_fwd(x, ldx, w, ldw, y, ldy, rows, K, N, &c)) return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_f16: ") + why);
-    if (bias && (uintptr_t)bias % 4) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_linear_f16: a pointer is not aligned to a float");
+int run_fwd(const LinearChoice& c, const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const float* res, int64_t ldres, float* y,
+            int64_t ldy, int64_t rows, int K, int N, void* stream, const char* what) {
     GemmArgs g{};
-    g.A = x; g.lda = ldx; g.B = w; g.ldb = ldw; g.C = y; g.ldc = ldy; g.bias = bias;
+    g.A = x; g.lda = ldx; g.B = w; g.ldb = ldw; g.C = y; g.ldc = ldy; g.bias = bias; g.res = res; g.ldres = ldres;
     g.M = rows; g.N = N; g.R = K; g.chunk = K; g.vec_a = c.vec_x; g.vec_b = c.vec_w; g.mma = 1;
     launch<true, true>(g, 1, static_cast<hipStream_t>(stream));
-    return hip_rc(hipGetLastError(), "ftc_text_linear_f16");
+    return hip_rc(hipGetLastError(), what);
 }
 
-int64_t ftc_text_linear_f16_bwd_workspace_bytes(int64_t rows, int K, int N) {
-    if (const char* why = linear_dims_refused(rows, K, N)) {
-        ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_f16_bwd_workspace_bytes: ") + why);
-        return -1;
-    }
-    return 4 * linear_workspace_floats(rows, K, N);
-}
-
-int ftc_text_linear_f16_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* dy, int64_t lddy, float* dx, int64_t lddx, float* dw,
-                            int64_t lddw, float* dbias, int64_t rows, int K, int N, void* workspace, void* stream) {
-    LinearChoice c;
-    if (const char* why = linear_resolve_bwd(x, ldx, w, ldw, dy, lddy, dx, lddx, dw, lddw, dbias, rows, K, N, workspace, &c))
-        return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_f16_bwd: ") + why);
+// the launches of a resolved backward call; dx_add (with dx) selects the data gradient's residual form
+int run_bwd(const LinearChoice& c, const float* x, int64_t ldx, const float* w, int64_t ldw, const float* dy, int64_t lddy, float* dx, int64_t lddx,
+            const float* dx_add, int64_t lddxa, float* dw, int64_t lddw, float* dbias, int64_t rows, int K, int N, void* workspace, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dx) {
         GemmArgs g{};
         g.A = dy; g.lda = lddy; g.B = w; g.ldb = ldw; g.C = dx; g.ldc = lddx;
         g.M = rows; g.N = K; g.R = N; g.chunk = N; g.vec_a = c.vec_dy; g.vec_b = 0; g.mma = 1;          // w lies along the output here: float by float
+        g.res = dx_add; g.ldres = lddxa;
         launch<true, false>(g, 1, s);
         if (int rc = hip_rc(hipGetLastError(), "ftc_text_linear_f16_bwd: data gradient")) return rc;
     }
@@ -267,6 +261,54 @@ int ftc_text_linear_f16_bwd(const float* x, int64_t ldx, const float* w, int64_t
         }
     }
     return FTC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ftc_text_linear_f16_abi_version(void) { return FTC_TEXT_LINEAR_F16_ABI_VERSION; }
+
+int ftc_text_linear_f16(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, float* y, int64_t ldy, int64_t rows, int K, int N,
+                        void* stream) {
+    LinearChoice c;
+    if (const char* why = linear_resolve_fwd(x, ldx, w, ldw, y, ldy, rows, K, N, &c)) return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_f16: ") + why);
+    if (bias && (uintptr_t)bias % 4) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_linear_f16: a pointer is not aligned to a float");
+    return run_fwd(c, x, ldx, w, ldw, bias, nullptr, 0, y, ldy, rows, K, N, stream, "ftc_text_linear_f16");
+}
+
+int ftc_text_linear_f16_res(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias, const float* res, int64_t ldres, float* y,
+                            int64_t ldy, int64_t rows, int K, int N, void* stream) {
+    LinearChoice c;
+    if (const char* why = linear_resolve_fwd_res(x, ldx, w, ldw, res, ldres, y, ldy, rows, K, N, &c))
+        return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_f16_res: ") + why);
+    if (bias && (uintptr_t)bias % 4) return ftc_set_error(FTC_ERR_INVALID, "ftc_text_linear_f16_res: a pointer is not aligned to a float");
+    return run_fwd(c, x, ldx, w, ldw, bias, res, ldres, y, ldy, rows, K, N, stream, "ftc_text_linear_f16_res");
+}
+
+int64_t ftc_text_linear_f16_bwd_workspace_bytes(int64_t rows, int K, int N) {
+    if (const char* why = linear_dims_refused(rows, K, N)) {
+        ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_f16_bwd_workspace_bytes: ") + why);
+        return -1;
+    }
+    return 4 * linear_workspace_floats(rows, K, N);
+}
+
+int ftc_text_linear_f16_bwd(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* dy, int64_t lddy, float* dx, int64_t lddx, float* dw,
+                            int64_t lddw, float* dbias, int64_t rows, int K, int N, void* workspace, void* stream) {
+    LinearChoice c;
+    if (const char* why = linear_resolve_bwd(x, ldx, w, ldw, dy, lddy, dx, lddx, dw, lddw, dbias, rows, K, N, workspace, &c))
+        return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_f16_bwd: ") + why);
+    return run_bwd(c, x, ldx, w, ldw, dy, lddy, dx, lddx, nullptr, 0, dw, lddw, dbias, rows, K, N, workspace, stream);
+}
+
+int ftc_text_linear_f16_bwd_add(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* dy, int64_t lddy, float* dx, int64_t lddx,
+                                const float* dx_add, int64_t lddxa, float* dw, int64_t lddw, float* dbias, int64_t rows, int K, int N, void* workspace,
+                                void* stream) {
+    LinearChoice c;
+    if (const char* why = linear_resolve_bwd_add(x, ldx, w, ldw, dy, lddy, dx, lddx, dx_add, lddxa, dw, lddw, dbias, rows, K, N, workspace, &c))
+        return ftc_set_error(FTC_ERR_INVALID, std::string("ftc_text_linear_f16_bwd_add: ") + why);
+    return run_bwd(c, x, ldx, w, ldw, dy, lddy, dx, lddx, dx_add, lddxa, dw, lddw, dbias, rows, K, N, workspace, stream);
 }
 
 }  // extern "C"

@@ -246,6 +246,7 @@ class RAdamScheduleFree(_MultiTensorOptimizer):
         self.__dict__.pop("_block", None)                # the copy's device schedule is made from its (synced) host values on its next step()
         if self._schedule == "device":
             self._step_supports_amp_scaling = True
+        self._state_replaced()
 
     def sync_schedule(self) -> None:
         """schedule="device": reads k, lr_max, weight_sum and scheduled_lr of every group back into ``param_groups`` -- one device-to-host copy,
@@ -263,7 +264,7 @@ class RAdamScheduleFree(_MultiTensorOptimizer):
         return super().state_dict()
 
     def load_state_dict(self, state_dict) -> None:
-        super().load_state_dict(state_dict)
+        super().load_state_dict(state_dict)              # whoever must know registers with register_load_state_dict_post_hook
         block = self.__dict__.get("_block")
         if block is not None:
             block["stale"] = True
@@ -274,6 +275,17 @@ class RAdamScheduleFree(_MultiTensorOptimizer):
         block = self.__dict__.get("_block")
         if block is not None:
             block["stale"] = True
+        self._state_replaced()
+
+    def add_invalidation_hook(self, hook: Callable[[], None]) -> None:
+        """``hook()`` is called whenever ``add_param_group`` or ``__setstate__`` (unpickling into this object) has changed which tensors the next
+        ``step()`` addresses or has marked the device schedule for upload: the events, next to ``load_state_dict`` (for which torch has
+        ``register_load_state_dict_post_hook``), after which a captured graph of ``step()`` replays stale pointers.  The hooks are not pickled."""
+        self.__dict__.setdefault("_invalidation_hooks", []).append(hook)
+
+    def _state_replaced(self) -> None:
+        for hook in self.__dict__.get("_invalidation_hooks", ()):
+            hook()
 
     def _device_block(self, dev: torch.device, n_chunks: int) -> dict:
         """One uint8 device buffer: 16 schedule states, 16 scalar blocks, the found-inf float, then one uint32 flag per chunk.  Made on the first

@@ -20,7 +20,10 @@ and ``TextGrad(model, linear="torch" | "hip" | "hip_fp16", attention="hip" | "hi
 training-mode forward + backward through those functions.  The linear layers (embed, the attention projections, the three SwiGLU matrices,
 the three output heads) go through ``torch.nn.functional.linear`` by default, through ``linear`` above with ``linear="hip"`` and through ``linear(..., operands="fp16")`` with
 ``linear="hip_fp16"``; the
-``torch.cat`` of ``[w1 | wg]`` and the ``+ _x`` that follows ``w2`` are torch ops either way.  The kernels' sums are in a fixed order: a call
+``torch.cat`` of ``[w1 | wg]`` and the ``+ _x`` that follows ``w2`` are torch ops either way -- unless ``ff="fused"`` (with ``linear="hip"`` or
+``"hip_fp16"``) makes the feed-forward block one autograd node: w1 / wg are then row slices of one ``[4E, E]`` buffer (names, order and values of
+``params`` unchanged), the ``+ x`` and the backward's ``dx + dy`` are added in the epilogues of ``include/ftc_text_linear_res.h``, and every result
+is the default's bit for bit.  The kernels' sums are in a fixed order: a call
 repeated on the same inputs leaves the same bits in every ``.grad`` that only these kernels produce -- with ``linear="hip"`` or
 ``"hip_fp16"`` that is every ``.grad``, and a batch row's logits do not depend on the rows it is batched with.
 
@@ -47,7 +50,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from .schema import modulo_list
 
-__all__ = ["attention", "rownorm", "swiglu", "loss_function3", "linear", "TextGrad"]
+__all__ = ["attention", "rownorm", "swiglu", "loss_function3", "linear", "TextGrad"]          # TextTrainStep (text_train_step.py) replays the step
 
 MASK_TOKEN = L.TEXT_MASK_TOKEN          # decoder_MSK
 _NO_CPU = "findtextcenternet_amd.text_grad runs on the GPU only, in fp32 (there is no CPU fallback)"
@@ -235,8 +238,8 @@ def swiglu(x: torch.Tensor) -> torch.Tensor:
 
 class _Linear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, bias, half):
-        _f32(x, w, bias)
+    def forward(ctx, x, w, bias, half, residual=None):
+        _f32(x, w, bias, residual)
         lib = L.load()
         fwd = lib.ftc_text_linear_f16 if half else lib.ftc_text_linear
         if w.dim() != 2 or x.dim() < 1 or x.shape[-1] != w.shape[1] or (bias is not None and bias.shape != (w.shape[0],)):
@@ -246,7 +249,15 @@ class _Linear(torch.autograd.Function):
         N, K = w.shape
         rows = x.numel() // K
         out = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
-        if rows:
+        if residual is not None:
+            if residual.shape != out.shape:
+                raise ValueError("linear: residual must have the shape of the result, [..., N]")
+            res = residual.contiguous()
+            if rows:
+                with torch.cuda.device(x.device):
+                    L.check((lib.ftc_text_linear_f16_res if half else lib.ftc_text_linear_res)(
+                        x.data_ptr(), K, w.data_ptr(), K, _ptr(b), res.data_ptr(), N, out.data_ptr(), N, rows, K, N, _stream(x.device)), "ftc_text_linear_res")
+        elif rows:
             with torch.cuda.device(x.device):
                 L.check(fwd(x.data_ptr(), K, w.data_ptr(), K, _ptr(b), out.data_ptr(), N, rows, K, N, _stream(x.device)), "ftc_text_linear")
         ctx.save_for_backward(x, w)
@@ -263,31 +274,93 @@ class _Linear(torch.autograd.Function):
         N, K = w.shape
         rows = x.numel() // K
         need = ctx.needs_input_grad
+        dres = dy if len(need) > 4 and need[4] else None          # the residual's gradient is dy itself
         dx = torch.empty_like(x) if need[0] else None
         dw = torch.empty_like(w) if need[1] else None
         db = torch.empty(N, dtype=torch.float32, device=w.device) if ctx.has_bias and need[2] else None
         if dx is None and dw is None and db is None:
-            return None, None, None, None
+            return None, None, None, None, dres
         if rows == 0:
             for t in (dw, db):
                 if t is not None:
                     t.zero_()
-            return dx, dw, db, None
+            return dx, dw, db, None, dres
         dy = dy.contiguous()
         with torch.cuda.device(x.device):
             ws = _ws(ws_bytes(rows, K, N) if dw is not None or db is not None else 0, x.device)
             L.check(bwd(x.data_ptr(), K, w.data_ptr(), K, dy.data_ptr(), N, _ptr(dx), K, _ptr(dw), K, _ptr(db), rows, K, N, ws.data_ptr(), _stream(x.device)),
                     "ftc_text_linear_bwd")
-        return dx, dw, db, None
+        return dx, dw, db, None, dres
 
 
-def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, operands: str = "fp32") -> torch.Tensor:
+def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, operands: str = "fp32",
+           residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [..., K] (made contiguous), w [N, K] as ``nn.Linear`` stores it, bias [N] or None -> x w^T + bias [..., N], with gradients.
     ``operands="fp32"``: ``include/ftc_text_linear.h``; ``operands="fp16"``: ``include/ftc_text_linear_f16.h`` (x, w and dy rounded to fp16 as they
-    are staged, fp32 sums, fp32 results).  The arithmetic and the order of every sum are the header's."""
+    are staged, fp32 sums, fp32 results).  The arithmetic and the order of every sum are the header's.  ``residual`` [..., N] (fp32, never
+    rounded) is added in the kernel's epilogue, after the bias (``include/ftc_text_linear_res.h``): the bits of ``linear(x, w, bias) + residual``
+    without the pass over the result; its gradient is the result's."""
     if operands not in ("fp32", "fp16"):
         raise ValueError(f"linear: operands must be 'fp32' or 'fp16', not {operands!r}")
-    return _Linear.apply(x, w, bias, operands == "fp16")
+    if residual is None:
+        return _Linear.apply(x, w, bias, operands == "fp16")
+    return _Linear.apply(x, w, bias, operands == "fp16", residual)
+
+
+class _FeedForward(torch.autograd.Function):
+    """The SwiGLU feed-forward block with its residual as ONE node (``TextGrad(ff="fused")``): y = x + w2 swiglu([w1 | wg] x + [b1 | bg]) + b2.
+    ``w14`` [4E, E] and ``b14`` [4E] are the buffers that the four leaves w1, wg, b1, bg are row slices of; the leaves are arguments only so that
+    autograd routes their gradients, which are the matching slices of one dW14 and one db14.  Three products forward (the wide layer, SwiGLU, the
+    narrow layer with ``+ x`` in its epilogue), and backward the narrow layer's three gradients, SwiGLU's, and the wide layer's with ``+ dy`` in the
+    data gradient's epilogue (``include/ftc_text_linear_res.h``): no concatenation, no split, no element-wise pass."""
+
+    @staticmethod
+    def forward(ctx, x, w1, wg, b1, bg, w2, b2, w14, b14, half):
+        _f32(x, w14, b14, w2, b2)
+        lib = L.load()
+        x = x.contiguous()
+        E, H2 = w14.shape[1], w14.shape[0]          # H2 = 2 * hidden
+        rows = x.numel() // E
+        dev = x.device
+        u = torch.empty(x.shape[:-1] + (H2,), dtype=torch.float32, device=dev)
+        s = torch.empty(x.shape[:-1] + (H2 // 2,), dtype=torch.float32, device=dev)
+        y = torch.empty_like(x)
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            L.check((lib.ftc_text_linear_f16 if half else lib.ftc_text_linear)(x.data_ptr(), E, w14.data_ptr(), E, b14.data_ptr(), u.data_ptr(), H2, rows, E, H2,
+                                                                                 st), "ftc_text_linear")
+            L.check(lib.ftc_text_swiglu(u.data_ptr(), s.data_ptr(), rows, H2 // 2, st), "ftc_text_swiglu")
+            L.check((lib.ftc_text_linear_f16_res if half else lib.ftc_text_linear_res)(s.data_ptr(), H2 // 2, w2.data_ptr(), H2 // 2, b2.data_ptr(), x.data_ptr(), E,
+                                                                                         y.data_ptr(), E, rows, H2 // 2, E, st), "ftc_text_linear_res")
+        ctx.save_for_backward(x, u, s, w14, w2)
+        ctx.half = half
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, u, s, w14, w2 = ctx.saved_tensors
+        lib = L.load()
+        half = ctx.half
+        bwd, ws_bytes = (lib.ftc_text_linear_f16_bwd, lib.ftc_text_linear_f16_bwd_workspace_bytes) if half else (
+            lib.ftc_text_linear_bwd, lib.ftc_text_linear_bwd_workspace_bytes)
+        bwd_add = lib.ftc_text_linear_f16_bwd_add if half else lib.ftc_text_linear_bwd_add
+        E, H2 = w14.shape[1], w14.shape[0]
+        H = H2 // 2
+        rows = x.numel() // E
+        dev = x.device
+        dy = dy.contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
+        ds, du, dx = new(rows, H), new(rows, H2), torch.empty_like(x)
+        dw2, db2, dw14, db14 = new(E, H), new(E), new(H2, E), new(H2)
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            ws = _ws(max(ws_bytes(rows, H, E), ws_bytes(rows, E, H2)), dev)          # the two calls run one after the other on the stream
+            L.check(bwd(s.data_ptr(), H, w2.data_ptr(), H, dy.data_ptr(), E, ds.data_ptr(), H, dw2.data_ptr(), H, db2.data_ptr(), rows, H, E, ws.data_ptr(), st),
+                    "ftc_text_linear_bwd")
+            L.check(lib.ftc_text_swiglu_bwd(u.data_ptr(), ds.data_ptr(), du.data_ptr(), rows, H, st), "ftc_text_swiglu_bwd")
+            L.check(bwd_add(x.data_ptr(), E, w14.data_ptr(), E, du.data_ptr(), H2, dx.data_ptr(), E, dy.data_ptr(), E, dw14.data_ptr(), E, db14.data_ptr(),
+                            rows, E, H2, ws.data_ptr(), st), "ftc_text_linear_bwd_add")
+        return dx, dw14[:H], dw14[H:], db14[:H], db14[H:], dw2, db2, None, None, None
 
 
 def _hip_linear(x, w, bias=None):          # TextGrad's constructor has an argument named `linear`
@@ -299,6 +372,7 @@ def _hip_linear_f16(x, w, bias=None):
 
 
 _LINEARS = {"torch": F.linear, "hip": _hip_linear, "hip_fp16": _hip_linear_f16}
+_FFS = ("torch", "fused")
 _ATTENTIONS = {"hip": "fp32", "hip_fp16": "fp16"}          # TextGrad's attention= -> attention()'s operands=
 
 
@@ -362,10 +436,17 @@ class TextGrad:
     ``operands="fp16"``: see the module's docstring for what stays fp32).  ``attention``: ``"hip"`` (fp32 fused attention, the default) or
     ``"hip_fp16"`` (``attention(..., operands="fp16")`` in the encoder's self-attention and the decoder's self- and cross-attention).
     With ``linear="hip_fp16"`` it is the faster step (40.1 ms against 49.2 ms at B = 8 on the default recognizer) and the one that
-    has the shape of the reference's AMP step; run it with a ``grad_scale``."""
+    has the shape of the reference's AMP step; run it with a ``grad_scale``.  ``ff``: ``"torch"`` (the default: ``torch.cat`` and a torch ``+ x`` around
+    the block's two linear layers) or ``"fused"`` (one node on the residual linear kernels, w1 / wg views of one buffer; the same bits)."""
 
-    def __init__(self, model, device=None, linear="torch", attention="hip"):
+    def __init__(self, model, device=None, linear="torch", attention="hip", ff="torch"):
         from .transformer import Transformer
+        if ff not in _FFS:
+            raise ValueError(f"TextGrad: ff must be 'torch' or 'fused', not {ff!r}")
+        if ff == "fused" and linear == "torch":
+            raise ValueError("TextGrad: ff='fused' is built on the HIP linear layers: it needs linear='hip' or 'hip_fp16'")
+        self.ff = ff
+        self._ff_buffers: Dict[str, tuple] = {}          # ff="fused": block prefix -> ([w1 | wg] [4E, E], [b1 | bg] [4E])
         if linear not in _LINEARS:
             raise ValueError(f"TextGrad: linear must be 'torch', 'hip' or 'hip_fp16', not {linear!r}")
         if attention not in _ATTENTIONS:
@@ -388,12 +469,32 @@ class TextGrad:
 
     def load_from_module(self) -> None:
         with torch.no_grad():
-            for n, p in self.model.named_parameters():
+            named = dict(self.model.named_parameters())
+            for n, p in named.items():
                 t = p.detach().to(device=self.device, dtype=torch.float32).contiguous().clone()
                 if n in self.params:
                     self.params[n].data.copy_(t)
+                elif self.ff == "fused" and n.endswith((".ff.w1.weight", ".ff.wg.weight", ".ff.w1.bias", ".ff.wg.bias")):
+                    self.params[n] = self._ff_view(n, t, named).requires_grad_(True)
                 else:
                     self.params[n] = t.requires_grad_(True)
+
+    def _ff_view(self, name: str, value: torch.Tensor, named) -> torch.Tensor:
+        """ff="fused": the leaf for w1 / wg (.weight or .bias) of a block, a contiguous row slice of the block's one [w1 | wg] buffer -- w1 in the
+        first half, as ``torch.cat([w1, wg])`` has it -- holding ``value``.  A leaf is a detached view: its own tensor to autograd and to the
+        optimizer, the buffer's memory to the kernels.  The slices start at multiples of 2E * E and 2E floats: 16-byte aligned as the whole is."""
+        prefix, layer, kind = name.rsplit(".", 2)
+        if prefix not in self._ff_buffers:
+            w1, wg = named[prefix + ".w1.weight"], named[prefix + ".wg.weight"]
+            if w1.shape != wg.shape or w1.shape[0] % 4:
+                raise ValueError("TextGrad: ff='fused' needs w1 and wg of one shape, rows a multiple of 4")
+            self._ff_buffers[prefix] = (torch.empty(2 * w1.shape[0], w1.shape[1], dtype=torch.float32, device=self.device),
+                                        torch.empty(2 * w1.shape[0], dtype=torch.float32, device=self.device))
+        buf = self._ff_buffers[prefix][0 if kind == "weight" else 1]
+        half = buf.shape[0] // 2
+        view = (buf[:half] if layer == "w1" else buf[half:]).detach()
+        view.copy_(value)
+        return view
 
     def store_to_module(self) -> None:
         with torch.no_grad():
@@ -422,6 +523,10 @@ class TextGrad:
 
     def _ff(self, p, x):
         P = self.params
+        if self.ff == "fused":
+            w14, b14 = self._ff_buffers[p]
+            return _FeedForward.apply(x, P[p + ".w1.weight"], P[p + ".wg.weight"], P[p + ".w1.bias"], P[p + ".wg.bias"], P[p + ".w2.weight"], P[p + ".w2.bias"],
+                                      w14, b14, self.linear == "hip_fp16")
         w = torch.cat([P[p + ".w1.weight"], P[p + ".wg.weight"]], 0)
         bias = torch.cat([P[p + ".w1.bias"], P[p + ".wg.bias"]], 0)
         return self._lin(swiglu(self._lin(x, w, bias)), P[p + ".w2.weight"], P[p + ".w2.bias"]) + x          # x + _x

@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Times the recognizer's whole AMP training step -- ``TextGrad.forward_backward`` (linear="hip_fp16", attention="hip_fp16", the default recognizer,
-B rows of 400 positions) followed by ``scaler.step(opt); scaler.update()`` -- with the two ways of driving the optimizer:
+B rows of 400 positions) followed by ``scaler.step(opt); scaler.update()`` -- with the two ways of driving the optimizer, the fused feed-forward
+block, and the whole step as one graph replay:
 
   host_gradscaler     RAdamScheduleFree(schedule="host") under torch.amp.GradScaler, grad_scale = 65536.0: the generic path (an unscale pass over the
                       416 gradients, found_inf.item(), then step());
   device_ampscaler    RAdamScheduleFree(schedule="device") under AmpScaler, grad_scale = scaler.scale_tensor: no host read of the device in the step.
+  device_ampscaler_fused_ff   the same, eager, on TextGrad(ff="fused"): no torch.cat of [w1 | wg], the block's two additions in the kernels' epilogues;
+  graph_ampscaler     TextTrainStep on TextGrad(ff="fused"): three input copies and one graph launch per step.  ``capture_ms`` is what its first two
+                      calls cost together (the eager warm-up, then capture + first replay), the gradient copy pass included;
+                      ``grad_copy_ms`` is that pass alone (one ``_foreach_copy_`` over the gradients), timed on its own.
 
 Three numbers per variant.  ``step_ms``: one step, the device synchronised before and after -- what the step costs when something waits for it anyway.
 ``issue_ms``: the part of that window in which the host was still issuing the step (the time until the Python call returned); where it is all but
@@ -31,7 +36,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 
-from findtextcenternet_amd import AmpScaler, ModelDimensions, RAdamScheduleFree, Transformer, recognizer_state_dict  # noqa: E402
+from findtextcenternet_amd import AmpScaler, ModelDimensions, RAdamScheduleFree, TextTrainStep, Transformer, recognizer_state_dict  # noqa: E402
 from findtextcenternet_amd.text_grad import TextGrad  # noqa: E402
 
 
@@ -56,9 +61,10 @@ def variants(dev, B):
     label = torch.randint(0x20, 0x30000, (B, S), generator=g)
     dec = torch.where(torch.rand(B, S, generator=g) < 0.5, torch.full_like(label, 3), label)
     enc, dec, label = enc.to(dev), dec.to(dev), label.to(dev)
-    out = {}
-    for name, schedule in (("host_gradscaler", "host"), ("device_ampscaler", "device")):
-        tg = TextGrad(model, device=dev, linear="hip_fp16", attention="hip_fp16")
+    out, extra = {}, {}
+    for name, schedule, ff in (("host_gradscaler", "host", "torch"), ("device_ampscaler", "device", "torch"), ("device_ampscaler_fused_ff", "device", "fused"),
+                               ("graph_ampscaler", "device", "fused")):
+        tg = TextGrad(model, device=dev, linear="hip_fp16", attention="hip_fp16", ff=ff)
         opt = RAdamScheduleFree(tg.parameters(), lr=2e-4, schedule=schedule)
         opt.train()
         if schedule == "host":
@@ -68,13 +74,24 @@ def variants(dev, B):
         else:
             scaler = AmpScaler(init_scale=65536.0)
             scale = scaler.scale_tensor
+        if name == "graph_ampscaler":
+            graph = TextTrainStep(tg, opt, scaler)
+            extra["capture_ms"] = round(timed(lambda: (graph(enc, dec, label), graph(enc, dec, label)))[1], 4)
+            assert graph.captures == 1
+            grads = [p.grad for p in tg.parameters() if p.grad is not None]
+            fresh = [torch.empty_like(g) for g in grads]
+            torch._foreach_copy_(fresh, grads)
+            extra["grad_copy_ms"] = round(statistics.median(timed(lambda: torch._foreach_copy_(fresh, grads))[1] for _ in range(5)), 4)
+            extra["grad_bytes"] = int(sum(g.numel() for g in grads) * 4)
+            out[name] = lambda graph=graph: graph(enc, dec, label)
+            continue
 
         def step(tg=tg, opt=opt, scaler=scaler, scale=scale):
             tg.forward_backward(enc, dec, label, grad_scale=scale)
             scaler.step(opt)
             scaler.update()
         out[name] = step
-    return out, dict(B=B, S=S, embed_dim=dims.embed_dim, heads=dims.head_num, enc_blocks=dims.enc_block_num, dec_blocks=dims.dec_block_num)
+    return out, extra, dict(B=B, S=S, embed_dim=dims.embed_dim, heads=dims.head_num, enc_blocks=dims.enc_block_num, dec_blocks=dims.dec_block_num)
 
 
 def main():
@@ -88,7 +105,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("text_step_bench.py: needs an MI355X (there is no CPU path to time)")
     dev = torch.device("cuda:0")
-    vs, shape = variants(dev, a.batch)
+    vs, extra, shape = variants(dev, a.batch)
     times = {(k, kind): [] for k in vs for kind in ("step", "issue", "pipelined")}
     for it in range(a.warmup + a.repeats):
         for k, fn in vs.items():
@@ -100,12 +117,17 @@ def main():
                 times[k, "issue"].append(issue)
                 times[k, "pipelined"].append(chain)
     res = {"tool": "text_step_bench", "repeats": a.repeats, "warmup": a.warmup, "chain": a.chain, "shape": shape}
+    res.update({f"graph_ampscaler_{k}": v for k, v in extra.items()})
     for (k, kind), ts in times.items():
         res[f"{k}_{kind}_ms"] = round(statistics.median(ts), 4)
         res[f"{k}_{kind}_spread"] = round((max(ts) - min(ts)) / statistics.median(ts), 4)
     for kind in ("step", "pipelined"):
         h, d = times["host_gradscaler", kind], times["device_ampscaler", kind]
         res[f"{kind}_device_faster_beyond_spread"] = bool(statistics.median(h) - statistics.median(d) > (max(h) - min(h)) + (max(d) - min(d)))
+        # a gain is claimed only where the medians differ by more than the sum of the two spreads: both against the unfused eager device step of this run
+        for k in ("device_ampscaler_fused_ff", "graph_ampscaler"):
+            f = times[k, kind]
+            res[f"{kind}_{k}_faster_beyond_spread"] = bool(statistics.median(d) - statistics.median(f) > (max(d) - min(d)) + (max(f) - min(f)))
     line = json.dumps(res)
     print(line)
     if a.json:
