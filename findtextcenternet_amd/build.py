@@ -32,8 +32,9 @@ EXTRA_DEPS.update({"text_linear_f16.hip": [os.path.join(os.path.dirname(HERE), "
                                            os.path.join(os.path.dirname(HERE), "include", "ftc_text_linear.h"),
                                            os.path.join(CSRC, "text_linear_choice.h")]})      # the same layers on fp16 operands: the same choice header
 TEXT_LINEAR_RES_H = os.path.join(os.path.dirname(HERE), "include", "ftc_text_linear_res.h")      # the residual forms: entry points in both sources
-EXTRA_DEPS["text_linear.hip"].append(TEXT_LINEAR_RES_H)
-EXTRA_DEPS["text_linear_f16.hip"].append(TEXT_LINEAR_RES_H)
+TEXT_LINEAR_IMPL_H = os.path.join(CSRC, "text_linear_impl.h")      # the tile loop, the launches and the entry points' bodies: each source adds its operands
+EXTRA_DEPS["text_linear.hip"] += [TEXT_LINEAR_RES_H, TEXT_LINEAR_IMPL_H]
+EXTRA_DEPS["text_linear_f16.hip"] += [TEXT_LINEAR_RES_H, TEXT_LINEAR_IMPL_H]
 EXTRA_DEPS.update({"text_attention_f16.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_text_attention_f16.h")]})      # attention on fp16 operands
 TEXT_ATTENTION16_H = os.path.join(os.path.dirname(HERE), "include", "ftc_text_attention16.h")      # inference attention on fp16 / bf16 operands, and the handle's switch
 EXTRA_DEPS.update({"text_attention_16.hip": [TEXT_ATTENTION16_H]})

@@ -1,7 +1,9 @@
 // The launch choice of the recognizer's linear layers (include/ftc_text_linear.h), made in ONE place: linear_resolve() turns the arguments of
 // ftc_text_linear / ftc_text_linear_bwd into the reason the call is refused or into the LinearChoice the launcher runs -- the row chunks of the
 // weight gradient, the grids, and per operand whether its base and pitch allow 16-byte reads.  ftc_text_linear_bwd_workspace_bytes reads the same
-// chunk rule.  Host only: the standard library, no HIP header and no kernel -- a plain C++ program can include it.
+// chunk rule.  The one launcher (text_linear_impl.h) runs every LinearChoice as it stands for both operand formats, text_linear.hip and
+// text_linear_f16.hip: the grids too, counted in tiles of TL_WG, which the launcher asserts is each format's tile; a loader that has no use for a
+// 16-byte flag ignores it.  Host only: the standard library, no HIP header and no kernel -- a plain C++ program can include it.
 #pragma once
 #include <cstdint>
 

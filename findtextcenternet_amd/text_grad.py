@@ -236,12 +236,18 @@ def swiglu(x: torch.Tensor) -> torch.Tensor:
     return _SwiGLU.apply(x)
 
 
+def _linear_calls(half: bool):
+    """The library's linear calls for one operand mode, fp16 (``half``) or fp32: forward, forward with residual, backward, backward with ``dx_add``,
+    and the backward's workspace size."""
+    lib, name = L.load(), "ftc_text_linear_f16" if half else "ftc_text_linear"
+    return tuple(getattr(lib, name + suffix) for suffix in ("", "_res", "_bwd", "_bwd_add", "_bwd_workspace_bytes"))
+
+
 class _Linear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, half, residual=None):
         _f32(x, w, bias, residual)
-        lib = L.load()
-        fwd = lib.ftc_text_linear_f16 if half else lib.ftc_text_linear
+        fwd, fwd_res, _, _, _ = _linear_calls(half)
         if w.dim() != 2 or x.dim() < 1 or x.shape[-1] != w.shape[1] or (bias is not None and bias.shape != (w.shape[0],)):
             raise ValueError("linear: x [..., K], w [N, K], bias [N] or None")
         x, w = x.contiguous(), w.contiguous()
@@ -255,7 +261,7 @@ class _Linear(torch.autograd.Function):
             res = residual.contiguous()
             if rows:
                 with torch.cuda.device(x.device):
-                    L.check((lib.ftc_text_linear_f16_res if half else lib.ftc_text_linear_res)(
+                    L.check(fwd_res(
                         x.data_ptr(), K, w.data_ptr(), K, _ptr(b), res.data_ptr(), N, out.data_ptr(), N, rows, K, N, _stream(x.device)), "ftc_text_linear_res")
         elif rows:
             with torch.cuda.device(x.device):
@@ -268,9 +274,7 @@ class _Linear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        lib = L.load()
-        bwd, ws_bytes = (lib.ftc_text_linear_f16_bwd, lib.ftc_text_linear_f16_bwd_workspace_bytes) if ctx.half else (
-            lib.ftc_text_linear_bwd, lib.ftc_text_linear_bwd_workspace_bytes)
+        _, _, bwd, _, ws_bytes = _linear_calls(ctx.half)
         N, K = w.shape
         rows = x.numel() // K
         need = ctx.needs_input_grad
@@ -318,6 +322,7 @@ class _FeedForward(torch.autograd.Function):
     def forward(ctx, x, w1, wg, b1, bg, w2, b2, w14, b14, half):
         _f32(x, w14, b14, w2, b2)
         lib = L.load()
+        fwd, fwd_res, _, _, _ = _linear_calls(half)
         x = x.contiguous()
         E, H2 = w14.shape[1], w14.shape[0]          # H2 = 2 * hidden
         rows = x.numel() // E
@@ -327,11 +332,10 @@ class _FeedForward(torch.autograd.Function):
         y = torch.empty_like(x)
         with torch.cuda.device(dev):
             st = _stream(dev)
-            L.check((lib.ftc_text_linear_f16 if half else lib.ftc_text_linear)(x.data_ptr(), E, w14.data_ptr(), E, b14.data_ptr(), u.data_ptr(), H2, rows, E, H2,
-                                                                                 st), "ftc_text_linear")
+            L.check(fwd(x.data_ptr(), E, w14.data_ptr(), E, b14.data_ptr(), u.data_ptr(), H2, rows, E, H2, st), "ftc_text_linear")
             L.check(lib.ftc_text_swiglu(u.data_ptr(), s.data_ptr(), rows, H2 // 2, st), "ftc_text_swiglu")
-            L.check((lib.ftc_text_linear_f16_res if half else lib.ftc_text_linear_res)(s.data_ptr(), H2 // 2, w2.data_ptr(), H2 // 2, b2.data_ptr(), x.data_ptr(), E,
-                                                                                         y.data_ptr(), E, rows, H2 // 2, E, st), "ftc_text_linear_res")
+            L.check(fwd_res(s.data_ptr(), H2 // 2, w2.data_ptr(), H2 // 2, b2.data_ptr(), x.data_ptr(), E, y.data_ptr(), E, rows, H2 // 2, E, st),
+                    "ftc_text_linear_res")
         ctx.save_for_backward(x, u, s, w14, w2)
         ctx.half = half
         return y
@@ -340,10 +344,7 @@ class _FeedForward(torch.autograd.Function):
     def backward(ctx, dy):
         x, u, s, w14, w2 = ctx.saved_tensors
         lib = L.load()
-        half = ctx.half
-        bwd, ws_bytes = (lib.ftc_text_linear_f16_bwd, lib.ftc_text_linear_f16_bwd_workspace_bytes) if half else (
-            lib.ftc_text_linear_bwd, lib.ftc_text_linear_bwd_workspace_bytes)
-        bwd_add = lib.ftc_text_linear_f16_bwd_add if half else lib.ftc_text_linear_bwd_add
+        _, _, bwd, bwd_add, ws_bytes = _linear_calls(ctx.half)
         E, H2 = w14.shape[1], w14.shape[0]
         H = H2 // 2
         rows = x.numel() // E
