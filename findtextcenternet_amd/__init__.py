@@ -10,7 +10,8 @@ from .weights import deterministic_state_dict, load_tf_efficientnetv2_npz, recog
 from .page import PageDetector, linedetect_parse, linedetect_request, page_merge_gpu   # noqa: F401
 from .prelabel import prelabel_file, prelabel_page, sample_page   # noqa: F401
 from .ocr import OCR_hip_Processer, build_result, plan_chunks, pool_plans, recognize_layout, recognize_layouts, run_pages   # noqa: F401
-from .optim import AdamWScheduleFree, AmpScaler, RAdamScheduleFree   # noqa: F401
+from .optim import AdamWScheduleFree, AmpScaler, RAdam, RAdamScheduleFree   # noqa: F401
+from .colour_jitter import ColorJitter, JitterParams   # noqa: F401
 from .train_step import TrainStep   # noqa: F401
 from .text_grad import TextGrad   # noqa: F401
 from .text_train_step import TextTrainStep   # noqa: F401
@@ -22,7 +23,7 @@ from . import synth   # noqa: F401
 
 __all__ = ["TextDetectorModel", "CenterNetDetection", "CenterNetDetector", "SimpleDecoder", "CodeDecoder", "decode_glyphs", "crt_codepoint", "HipDetectorBackend", "ModelDimensions", "Transformer", "TransformerPredictor", "HipTextBackend", "recognize_chunks", "recognizer_state_dict",
            "TileGeom", "Decoded", "decode_peaks", "tiles_to_device", "exact_logit_cut", "tile_keep_rect", "deterministic_state_dict", "load_tf_efficientnetv2_npz", "PageDetector", "page_merge_gpu", "linedetect_request",
-           "linedetect_parse", "prelabel_page", "prelabel_file", "sample_page", "OCR_hip_Processer", "plan_chunks", "build_result", "recognize_layout", "recognize_layouts", "pool_plans", "run_pages", "AdamWScheduleFree", "RAdamScheduleFree", "AmpScaler", "TextGrad", "TextTrainStep", "TrainStep", "DetectorLanes",
+           "linedetect_parse", "prelabel_page", "prelabel_file", "sample_page", "OCR_hip_Processer", "plan_chunks", "build_result", "recognize_layout", "recognize_layouts", "pool_plans", "run_pages", "AdamWScheduleFree", "RAdamScheduleFree", "RAdam", "ColorJitter", "JitterParams", "AmpScaler", "TextGrad", "TextTrainStep", "TrainStep", "DetectorLanes",
            "SampleSynth", "Page", "PageMeta", "CropParams", "ColourParams", "draw_crop_params", "draw_colour_params", "draw_bg_offset", "SaltParams", "DistortParams", "draw_salt_params", "draw_distort_params", "draw_augment",
            "gaussian_weights", "host_minsize", "TextFeatureBank", "TextParams", "TextSampleSynth", "draw_text_params",
            "width", "height", "scale", "feature_dim", "modulo_list"]

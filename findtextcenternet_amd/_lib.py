@@ -82,6 +82,15 @@ FTC_OPTIM_AMP_ABI_VERSION = 1
 RADAM_MAX_GROUPS = 16
 OPTIM_AMP_EXPORTS = ["ftc_optim_amp_abi_version", "ftc_amp_nonfinite_scan", "ftc_radam_sf_schedule", "ftc_radam_schedulefree_step_dev"]
 
+# include/ftc_optim_radam.h (the detector fine-tune's optimizer: one step of plain torch.optim.RAdam over an MtChunk table)
+FTC_OPTIM_RADAM_ABI_VERSION = 1
+OPTIM_RADAM_EXPORTS = ["ftc_optim_radam_abi_version", "ftc_radam_step"]
+
+# include/ftc_colour_jitter.h (torchvision's ColorJitter on a device batch)
+FTC_COLOUR_JITTER_ABI_VERSION = 1
+CJ_BLOCK = 4096
+CJ_BRIGHTNESS, CJ_CONTRAST, CJ_SATURATION, CJ_HUE = range(4)
+COLOUR_JITTER_EXPORTS = ["ftc_colour_jitter_abi_version", "ftc_colour_jitter_workspace_bytes", "ftc_colour_jitter"]
 
 # include/ftc_ocr.h (page-level OCR glue): again its own version and list
 FTC_OCR_ABI_VERSION = 1
@@ -169,6 +178,11 @@ class RadamScalars(C.Structure):
     """ftc_radam_scalars of include/ftc_optim_amp.h: 48 bytes."""
     _fields_ = [(n, C.c_float) for n in ("beta2", "one_minus_beta2", "bias_correction2", "eps", "weight_decay", "ckp1", "y_alpha", "lr", "inv_scale")] + [
         (n, C.c_int32) for n in ("adam", "skip", "reserved")]
+
+
+class CjDesc(C.Structure):
+    """ftc_cj_desc of include/ftc_colour_jitter.h: 48 bytes."""
+    _fields_ = [("order", C.c_int32 * 4), ("factor", C.c_float * 4), ("mask", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class PackEntry(C.Structure):
@@ -365,6 +379,12 @@ def load():
     lib.ftc_amp_nonfinite_scan.argtypes = [vp, i32, vp, vp]
     lib.ftc_radam_sf_schedule.argtypes = [C.POINTER(RadamHyper), i32, vp, i32, vp, vp, vp, vp, vp, vp]
     lib.ftc_radam_schedulefree_step_dev.argtypes = [vp, i32, vp, i32, vp]
+    lib.ftc_optim_radam_abi_version.restype = i32
+    lib.ftc_radam_step.argtypes = [vp, i32] + [C.c_float] * 10 + [i32, i32, vp]
+    lib.ftc_colour_jitter_abi_version.restype = i32
+    lib.ftc_colour_jitter_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.ftc_colour_jitter_workspace_bytes.restype = i64
+    lib.ftc_colour_jitter.argtypes = [C.POINTER(CjDesc), vp, i32, i32, i32, vp, vp, vp, C.c_size_t, vp]
     lib.ftc_ocr_abi_version.restype = i32
     lib.ftc_ocr_assemble.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp, vp]
     lib.ftc_prep_abi_version.restype = i32
@@ -384,6 +404,10 @@ def load():
     lib.ftc_text_sample_abi_version.restype = i32
     lib.ftc_text_bank_init.argtypes = [C.POINTER(TextBank), vp, C.POINTER(TextBankEntry), vp, i32, i32]
     lib.ftc_text_sample.argtypes = [C.POINTER(TextBank), C.POINTER(TextSampleDesc), vp, i32, vp, i64, vp, i32, vp, vp, vp]
+    if lib.ftc_colour_jitter_abi_version() != FTC_COLOUR_JITTER_ABI_VERSION:
+        raise FtcLibraryError(f"colour jitter ABI mismatch: library {lib.ftc_colour_jitter_abi_version()} vs binding {FTC_COLOUR_JITTER_ABI_VERSION}")
+    if lib.ftc_optim_radam_abi_version() != FTC_OPTIM_RADAM_ABI_VERSION:
+        raise FtcLibraryError(f"RAdam ABI mismatch: library {lib.ftc_optim_radam_abi_version()} vs binding {FTC_OPTIM_RADAM_ABI_VERSION}")
     if lib.ftc_text_sample_abi_version() != FTC_TEXT_SAMPLE_ABI_VERSION:
         raise FtcLibraryError(f"text sample ABI mismatch: library {lib.ftc_text_sample_abi_version()} vs binding {FTC_TEXT_SAMPLE_ABI_VERSION}")
     if lib.ftc_sample_aug_abi_version() != FTC_SAMPLE_AUG_ABI_VERSION:

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libftc_hip.so")
 SOURCES = ["conv_igemm_bf16_fb.hip", "conv_igemm_bf16_ff.hip", "conv_igemm_f16_fh.hip", "conv_igemm_f16_ff.hip",
-           "conv_igemm_f32.hip", "conv_igemm_x3.hip", "conv_igemm.hip", "conv1x1_px144.hip", "backbone_ops.hip", "mbconv_slice.hip", "mbconv_slice_x3.hip", "fused_mbconv.hip", "conv3x3_c32.hip", "fpn_ops.hip", "decode.hip", "glyph_select.hip", "maskpredict_select.hip", "text_attention.hip", "text_ops.hip", "ftc_text.hip", "text_attention_bwd.hip", "text_ops_bwd.hip", "text_loss.hip", "text_linear.hip", "text_linear_f16.hip", "text_attention_f16.hip", "text_attention_16.hip", "ocr_assemble.hip", "page_ops.hip", "page_merge.hip", "page_fill.hip", "sample_synth.hip", "sample_distort.hip", "text_sample.hip", "optim.hip", "optim_radam.hip", "train_ops.hip", "bwd_ops.hip", "wgrad.hip", "ftc_api.hip", "pack.hip", "plan.hip", "model.hip"]
+           "conv_igemm_f32.hip", "conv_igemm_x3.hip", "conv_igemm.hip", "conv1x1_px144.hip", "backbone_ops.hip", "mbconv_slice.hip", "mbconv_slice_x3.hip", "fused_mbconv.hip", "conv3x3_c32.hip", "fpn_ops.hip", "decode.hip", "glyph_select.hip", "maskpredict_select.hip", "text_attention.hip", "text_ops.hip", "ftc_text.hip", "text_attention_bwd.hip", "text_ops_bwd.hip", "text_loss.hip", "text_linear.hip", "text_linear_f16.hip", "text_attention_f16.hip", "text_attention_16.hip", "ocr_assemble.hip", "page_ops.hip", "page_merge.hip", "page_fill.hip", "sample_synth.hip", "sample_distort.hip", "text_sample.hip", "optim.hip", "optim_radam.hip", "optim_radam_plain.hip", "colour_jitter.hip", "train_ops.hip", "bwd_ops.hip", "wgrad.hip", "ftc_api.hip", "pack.hip", "plan.hip", "model.hip"]
 HEADERS = [os.path.join(CSRC, "ftc_common.h"), os.path.join(CSRC, "conv_igemm_impl.h"), os.path.join(CSRC, "conv_choice.h"), os.path.join(CSRC, "wgrad_choice.h"), os.path.join(CSRC, "backbone_choice.h"), os.path.join(CSRC, "train_choice.h"), os.path.join(CSRC, "op_extents.h"), os.path.join(os.path.dirname(HERE), "include", "ftc.h"),
            os.path.join(CSRC, "ftc_host.h"), os.path.join(CSRC, "crt_wave.h"), os.path.join(CSRC, "text_math.h"), os.path.join(os.path.dirname(HERE), "include", "ftc_text.h")]
 EXTRA_DEPS = {"ocr_assemble.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_ocr.h")],
@@ -31,6 +31,8 @@ EXTRA_DEPS.update({"text_linear.hip": [os.path.join(os.path.dirname(HERE), "incl
 EXTRA_DEPS.update({"text_linear_f16.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_text_linear_f16.h"),
                                            os.path.join(os.path.dirname(HERE), "include", "ftc_text_linear.h"),
                                            os.path.join(CSRC, "text_linear_choice.h")]})      # the same layers on fp16 operands: the same choice header
+EXTRA_DEPS.update({"optim_radam_plain.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_optim_radam.h")],      # plain RAdam: the fine-tune loop's optimizer
+                   "colour_jitter.hip": [os.path.join(os.path.dirname(HERE), "include", "ftc_colour_jitter.h")]})      # ColorJitter on a device batch
 TEXT_LINEAR_RES_H = os.path.join(os.path.dirname(HERE), "include", "ftc_text_linear_res.h")      # the residual forms: entry points in both sources
 TEXT_LINEAR_IMPL_H = os.path.join(CSRC, "text_linear_impl.h")      # the tile loop, the launches and the entry points' bodies: each source adds its operands
 EXTRA_DEPS["text_linear.hip"] += [TEXT_LINEAR_RES_H, TEXT_LINEAR_IMPL_H]
@@ -47,7 +49,8 @@ EXTRA_DEPS.update({"pack.hip": [MODEL_NET_H], "plan.hip": [MODEL_NET_H, TUNING_I
 # sample_synth.hip, sample_distort.hip: the arithmetic contracts of include/ftc_sample.h and include/ftc_sample_aug.h (every product and sum
 # rounded on its own, as the reference's build and as NumPy / scipy evaluate them); text_sample.hip: the float64 add of include/ftc_text_sample.h
 EXTRA_FLAGS = {"pack.hip": ["-ffp-contract=off"], "plan.hip": ["-ffp-contract=off"], "maskpredict_select.hip": ["-ffp-contract=off"],
-               "sample_synth.hip": ["-ffp-contract=off"], "sample_distort.hip": ["-ffp-contract=off"], "text_sample.hip": ["-ffp-contract=off"]}
+               "sample_synth.hip": ["-ffp-contract=off"], "sample_distort.hip": ["-ffp-contract=off"], "text_sample.hip": ["-ffp-contract=off"],
+               "optim_radam_plain.hip": ["-ffp-contract=off"], "colour_jitter.hip": ["-ffp-contract=off"]}      # the contracts of include/ftc_optim_radam.h, include/ftc_colour_jitter.h
 
 
 def write_tuning_table() -> None:

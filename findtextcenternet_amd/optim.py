@@ -10,6 +10,9 @@ it unchanged.  ``step()`` is one HIP launch over all parameters of a group (``ft
 ``radam_step_scalars`` is its float64 schedule, ``step()`` one ``ftc_radam_schedulefree_step`` launch per group and ``train()`` /
 ``eval()`` one ``ftc_schedulefree_lerp`` launch per group (``include/ftc_optim.h``).  With ``schedule="device"`` the schedule lives on the GPU
 and the step unscales, checks and skips there (``include/ftc_optim_amp.h``); ``AmpScaler`` is the loss scaler for that mode.
+
+``RAdam`` is plain ``torch.optim.RAdam`` for the detector fine-tune (``train2.py:110``): ``radam_plain_scalars`` is torch's float64 derivation of a
+step's scalars, ``step()`` one ``ftc_radam_step`` launch per group (``include/ftc_optim_radam.h``).
 """
 from __future__ import annotations
 
@@ -91,8 +94,14 @@ _NOT_TRAIN = ("Optimizer was not in train mode when step is called. Please inser
 
 
 class _MultiTensorOptimizer(torch.optim.Optimizer):
-    """What the two Schedule-Free optimizers share: the per-parameter state (z, exp_avg_sq), the checks on what the 16-byte-lane kernels
-    can address, and the cached device table of chunk pointers (ftc_mt_chunk) that one launch walks."""
+    """What the multi-tensor optimizers share: the per-parameter state (for the two Schedule-Free ones z, exp_avg_sq), the checks on what the
+    16-byte-lane kernels can address, and the cached device table of chunk pointers (ftc_mt_chunk) that one launch walks."""
+
+    _STATE_NAMES = ("z", "exp_avg_sq")          # the state tensors behind the table's z and v columns
+
+    def _new_state(self, p: torch.Tensor, st: dict) -> None:
+        st[self._STATE_NAMES[0]] = torch.clone(p, memory_format=torch.preserve_format)
+        st[self._STATE_NAMES[1]] = torch.zeros_like(p, memory_format=torch.preserve_format)
 
     def _active(self, group: dict) -> List[torch.Tensor]:
         """The parameters of `group` that have a gradient, checked, their state created on first sight."""
@@ -102,41 +111,43 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
                 raise RuntimeError(f"findtextcenternet_amd.{type(self).__name__}: parameters and gradients must be contiguous fp32 "
                                    "CUDA tensors (no CPU fallback)")
             st = self.state[p]
-            if "z" not in st:
-                st["z"] = torch.clone(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if self._STATE_NAMES[0] not in st:
+                self._new_state(p, st)
         return active
 
-    def _chunk_table(self, gi: int, active: List[torch.Tensor], with_grad: bool = True) -> Tuple[torch.Tensor, int]:
+    def _chunk_table(self, gi: int, active: List[torch.Tensor], with_grad: bool = True, slot: int = 0) -> Tuple[torch.Tensor, int]:
         # The table holds raw device pointers of the parameter, its gradient AND its two state tensors, so all four are in the
         # cache key: load_state_dict(), state.clear() or a moved state tensor would otherwise leave the kernel writing through
         # stale pointers.  `_tables` is created lazily: Optimizer.__setstate__ (unpickle, deepcopy) does not restore it.
         # with_grad = False is the table of the train() / eval() swap, which reads no gradient (a parameter may have state and none):
-        # its g column is NULL and it is cached apart from the step's table.
+        # its g column is NULL and it is cached apart from the step's table.  slot tells apart the tables of one group where a step launches
+        # more than once (RAdam: one launch per distinct step value).
+        zn, vn = self._STATE_NAMES
+        where = (gi, with_grad) if slot == 0 else (gi, with_grad, slot)
         tables = self.__dict__.setdefault("_tables", {})
         g_ptr = (lambda p: p.grad.data_ptr()) if with_grad else (lambda p: 0)
-        key = tuple((p.data_ptr(), g_ptr(p), self.state[p]["z"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr(), p.numel()) for p in active)
-        hit = tables.get((gi, with_grad))
+        key = tuple((p.data_ptr(), g_ptr(p), self.state[p][zn].data_ptr(), self.state[p][vn].data_ptr(), p.numel()) for p in active)
+        hit = tables.get(where)
         if hit is not None and hit[0] == key:
             return hit[1], hit[2]
         rows = []
         for p in active:
             st = self.state[p]
             n = p.numel()
-            for name, t in (("parameter", p), ("gradient", p.grad if with_grad else p), ("z", st["z"]), ("exp_avg_sq", st["exp_avg_sq"])):
+            for name, t in (("parameter", p), ("gradient", p.grad if with_grad else p), (zn, st[zn]), (vn, st[vn])):
                 if t.data_ptr() % 16 or t.device != p.device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
                     raise RuntimeError(f"findtextcenternet_amd.{type(self).__name__}: {name} of a parameter is not a 16-byte aligned, "
                                        "contiguous fp32 tensor on the parameter's device (view parameters / bucket-view gradients "
                                        "are not supported by the 16-byte-lane kernel)")
             for off in range(0, n, CHUNK):
-                rows.append((p.data_ptr() + 4 * off, g_ptr(p) + 4 * off if with_grad else 0, st["exp_avg_sq"].data_ptr() + 4 * off,
-                             st["z"].data_ptr() + 4 * off, min(CHUNK, n - off)))
+                rows.append((p.data_ptr() + 4 * off, g_ptr(p) + 4 * off if with_grad else 0, st[vn].data_ptr() + 4 * off,
+                             st[zn].data_ptr() + 4 * off, min(CHUNK, n - off)))
         arr = (L.MtChunk * len(rows))()
         for i, (y, g, v, z, n) in enumerate(rows):
             arr[i].y, arr[i].g, arr[i].v, arr[i].z, arr[i].n = y, g, v, z, n
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         dev = host.to(active[0].device)
-        tables[(gi, with_grad)] = (key, dev, len(rows))
+        tables[where] = (key, dev, len(rows))
         return dev, len(rows)
 
 
@@ -413,6 +424,123 @@ class RAdamScheduleFree(_MultiTensorOptimizer):
                             "ftc_radam_schedulefree_step")
                 bump_versions(active)                # the kernel wrote through raw pointers: tell whoever fingerprints the parameters
             group["k"] = group["k"] + 1
+        return loss
+
+
+def radam_plain_scalars(group: dict, step: float) -> Dict[str, float]:
+    """The scalars of one torch.optim.RAdam step in float64 exactly as torch derives them (torch/optim/radam.py, _single_tensor_radam), for the
+    step value `step` (already advanced: 1.0 on the first step, a float as torch keeps it).  `adaptive` is torch's `rho_t > 5.0`: the rectified
+    Adam step; at and below it the step is the bias-corrected first moment times lr, and rect is not used (0 here)."""
+    beta1, beta2 = group["betas"]
+    lr, wd = float(group["lr"]), group["weight_decay"]
+    bias_correction1 = 1 - beta1 ** step
+    bias_correction2 = 1 - beta2 ** step
+    rho_inf = 2 / (1 - beta2) - 1                                          # maximum length of the approximated SMA
+    rho_t = rho_inf - 2 * step * (beta2 ** step) / bias_correction2        # its length at this step
+    adaptive = rho_t > 5.0
+    rect = ((rho_t - 4) * (rho_t - 2) * rho_inf / ((rho_inf - 4) * (rho_inf - 2) * rho_t)) ** 0.5 if adaptive else 0.0
+    return {"w1": 1 - beta1, "beta2": beta2, "one_minus_beta2": 1 - beta2, "bc1": bias_correction1, "sqrt_bc2": bias_correction2 ** 0.5, "lr": lr,
+            "eps": group["eps"], "weight_decay": wd, "decay_mul": 1 - lr * wd, "rect": rect, "adaptive": int(adaptive),
+            "decoupled": int(bool(group["decoupled_weight_decay"])), "rho_inf": rho_inf, "rho_t": rho_t}
+
+
+RADAM_PLAIN_FLOATS = ("w1", "beta2", "one_minus_beta2", "bc1", "sqrt_bc2", "lr", "eps", "weight_decay", "decay_mul", "rect")      # ftc_radam_step's order
+
+
+class RAdam(_MultiTensorOptimizer):
+    """``torch.optim.RAdam`` (the reference's ``train2.py:110``) on the MI355X path: the same constructor arguments and defaults, ``param_groups``
+    keys and per-parameter state (``step`` as torch keeps it -- a float32 CPU scalar tensor --, ``exp_avg``, ``exp_avg_sq``), so ``train2.py:110, 190,
+    203`` construct and drive it unchanged and a ``state_dict()`` moves to and from ``torch.optim.RAdam`` in both directions.  ``step()`` is one HIP
+    launch per group (``ftc_radam_step``, the per-element contract of ``include/ftc_optim_radam.h``) in place of torch's chain of ``_foreach_*``
+    passes; parameters and gradients must be contiguous fp32 CUDA tensors (there is no CPU fallback).
+
+    torch keeps ``step`` per parameter and a parameter without a gradient does not advance, so a group's active parameters are grouped by their step
+    value and each distinct value gets one launch: one launch per group in the normal case.  ``launches`` counts the ``ftc_radam_step`` calls made so far.
+    ``foreach`` is accepted and ignored; ``maximize``, ``differentiable`` and ``capturable`` are refused when set.  As in torch there is no
+    ``train()`` / ``eval()`` protocol."""
+
+    _STATE_NAMES = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr=1e-3, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0,
+                 decoupled_weight_decay: bool = False, *, foreach: Optional[bool] = None, maximize: bool = False, capturable: bool = False,
+                 differentiable: bool = False):
+        if isinstance(lr, torch.Tensor):
+            raise TypeError("findtextcenternet_amd.RAdam: lr must be a float (the step's scalars are computed on the host)")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, maximize=maximize, foreach=foreach, capturable=capturable,
+                        decoupled_weight_decay=decoupled_weight_decay, differentiable=differentiable)
+        super().__init__(params, defaults)
+        self._refuse_unsupported()
+        self.launches = 0
+
+    def _refuse_unsupported(self) -> None:
+        for group in self.param_groups:
+            for key in ("maximize", "differentiable", "capturable"):
+                if group.get(key, False):
+                    raise ValueError(f"findtextcenternet_amd.RAdam: {key}=True is not supported (the update is one HIP launch with host-side scalars)")
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self.__dict__.setdefault("launches", 0)
+        for group in self.param_groups:
+            for key, value in (("foreach", None), ("maximize", False), ("differentiable", False), ("capturable", False), ("decoupled_weight_decay", False)):
+                group.setdefault(key, value)
+
+    def _new_state(self, p: torch.Tensor, st: dict) -> None:
+        st["step"] = torch.tensor(0.0, dtype=torch.float32)                # torch's _get_scalar_dtype() default, on the CPU as without capturable
+        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
+    @torch.no_grad()
+    def step(self, closure: Optional[Callable[[], float]] = None) -> Optional[float]:
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._refuse_unsupported()
+        lib = L.load()
+        f = C.c_float
+        for gi, group in enumerate(self.param_groups):
+            active = self._active(group)
+            if not active:
+                continue
+            # torch's bookkeeping, step += 1 on every active parameter, as one foreach add; the values are mirrored on the host (keyed by the
+            # tensor and its version counter) so that a step reads no tensor back unless somebody else wrote it
+            mirror = self.__dict__.setdefault("_step_mirror", {})
+            steps = []
+            by_step: Dict[float, List[torch.Tensor]] = {}
+            for p in active:
+                st = self.state[p]
+                t = st["step"]
+                if not torch.is_tensor(t):                                 # a state dict of an older torch keeps a number
+                    t = st["step"] = torch.tensor(float(t), dtype=torch.float32)
+                hit = mirror.get(p)
+                value = hit[2] if hit is not None and hit[0] is t and hit[1] == t._version else float(t)
+                steps.append(t)
+                mirror[p] = [t, None, value + 1.0]
+                by_step.setdefault(value + 1.0, []).append(p)
+            torch._foreach_add_(steps, 1.0)
+            for p in active:
+                mirror[p][1] = mirror[p][0]._version
+            dev = active[0].device
+            with torch.cuda.device(dev):
+                stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+                for slot, (step, ps) in enumerate(sorted(by_step.items())):
+                    sc = radam_plain_scalars(group, step)
+                    table, n = self._chunk_table(gi, ps, slot=slot)
+                    L.check(lib.ftc_radam_step(table.data_ptr(), n, *(f(sc[k]) for k in RADAM_PLAIN_FLOATS), sc["adaptive"], sc["decoupled"], stream),
+                            "ftc_radam_step")
+                    self.launches += 1
+            bump_versions(active)                    # the kernel wrote through raw pointers: tell whoever fingerprints the parameters
         return loss
 
 
